@@ -17,7 +17,10 @@ hashes in 16 FileSegments).  With --gpus N > 1 (the script launches its own N ra
 DESIGN.md 6 says why the default is what it is: in the packed form a query hash costs one HBM line whatever the number of columns behind it,
 so sharding the SEGMENTS does not divide a rank's work, and sharding the HASH SPACE leaves every rank the bookkeeping of all the queries.
 
-Prints ONE JSON line (rank 0).  At N = 1 the line also carries, measured in the same run:
+Prints ONE JSON line (rank 0).  A plain run does what the headline needs and nothing else: it builds the index, warms up, times the
+--steps steps, writes the last timed step's results when --dump-outputs DIR is given, and prints the line.  With --full it also times
+the same steps again over >= 200 steps (`value_long`, `repeated_batch`) and measures the streaming / random read bandwidth, and at
+N = 1 the line also carries, measured in the same run:
   roofline      physical bytes of the dominant kernel / its HIP-event time / 8 TB/s (<= 1); `traffic` = HBM bytes by PMC
                 from a rocprofv3 child pass of this very script (or, if that is unavailable, from profiles/ with the
                 kernels' source hash attached); the reference-equivalent figure of SURVEY 8(d) is kept separately
@@ -81,6 +84,14 @@ def parse_args():
     ap.add_argument("--no-extras", action="store_true", help="headline only: no by_batch / end_to_end / config1 / pmc child")
     ap.add_argument("--no-pmc", action="store_true", help="do not spawn the rocprofv3 --pmc FETCH_SIZE child pass")
     ap.add_argument("--pmc-child", action="store_true", help=argparse.SUPPRESS)     # internal: the profiled child
+    ap.add_argument("--full", action="store_true",
+                    help="everything besides the headline: the long and repeated-batch runs, the measured bandwidth, and at N = 1 the tables, "
+                         "the other configurations, the PMC passes, the block form, the hot-hash data and the CPU baseline (the --no-* "
+                         "options above narrow it down)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last timed step returned as DIR/<name>.npy (float64): doc_ids and "
+                         "scores [B, cap] (zero past a query's count), counts [B]; a seeded sample of the queries (query_index) if that "
+                         "exceeds 64 MB")
     return ap.parse_args()
 
 
@@ -371,6 +382,30 @@ def host_memory_available():
     return None
 
 
+DUMP_MAX_BYTES = 64 << 20
+
+
+def dump_outputs(d, out, out_n):
+    """--dump-outputs: the results of the last timed step as a caller of fpx_search_resident receives them -- doc id and score of every
+    hit [B, cap], the number of hits [B] -- in float64 (doc ids exceed float32's 2^24).  The slots past a query's count hold nothing a
+    caller may read: they are written as 0.  Above 64 MB in all, a fixed seeded sample of the queries, named by query_index."""
+    os.makedirs(d, exist_ok=True)
+    B, cap = out.shape[0], out.shape[1]
+    rows = np.arange(B)
+    per_row = (2 * cap + 2) * 8
+    if B * per_row > DUMP_MAX_BYTES:
+        rows = np.sort(np.random.default_rng(0).choice(B, (DUMP_MAX_BYTES - 4096) // per_row, replace=False))     # (4 KB: the files' headers)
+    n = out_n[rows].astype(np.int64)
+    valid = np.arange(cap)[None, :] < n[:, None]
+    arrays = {"doc_ids": np.where(valid, out[rows, :, 0], 0), "scores": np.where(valid, out[rows, :, 1], 0), "counts": n}
+    if len(rows) < B:
+        arrays["query_index"] = rows
+    elif os.path.exists(os.path.join(d, "query_index.npy")):
+        os.remove(os.path.join(d, "query_index.npy"))          # (a sample's index from an earlier run would name the wrong rows)
+    for name, a in arrays.items():
+        np.save(os.path.join(d, name + ".npy"), a.astype(np.float64))
+
+
 def cpu_baseline(fpx, oracle, segs, ranges, flat, offsets, nq, opts, gpu_lists, target_s):
     """The oracle (C restatement of the reference CPU path, SSSE3 decode like the reference) on this box's host cores:
     the WHOLE index downloaded from HBM into host RAM, the first `nq` queries of the batch, one search per thread on
@@ -527,6 +562,7 @@ def launch_check(rank, world):
 
 
 def main():
+    t_main = time.perf_counter()
     args = parse_args()
     if args.pmc_child:
         return pmc_child_main(args)
@@ -620,6 +656,32 @@ def main():
             shrunk = True
     per = docs // S
     docs = per * S
+
+    # ---- queries (identical on every rank), resident in HBM before the timed region: NQB DISTINCT batches (different seeds,
+    #      different targets, different noise) that the steps rotate through, so that no step finds the previous step's
+    #      directory lines and pages in the caches / TLBs (a repeated batch is the TLB's best case).  They are made on host threads
+    #      while the GPU builds the index (numpy and the library's calls release the GIL): seconds of set-up less, the same batches
+    NQB = max(1, int(os.environ.get("FPX_BENCH_QUERY_BATCHES", "8")))
+    opts = fpx.http_options(limit=args.limit, min_score=args.min_score)
+    # hash sharding, the ROUTED protocol (FPX_BENCH_ROUTED=0: round 3's, the whole batch's hashes on every rank): a rank holds only
+    # ITS share of the batch -- the queries it finishes -- and uploads nothing else
+    routed = shard_mode == "hash" and os.environ.get("FPX_BENCH_ROUTED", "1") != "0"
+    B_global = B
+    import concurrent.futures as cf
+    qpool = cf.ThreadPoolExecutor(4)
+    if routed:
+        bpr = fpx.shard_bins_per_rank(B_global, pw)
+        q_share = (min(B_global, rank * bpr * 8), min(B_global, (rank + 1) * bpr * 8))
+        B = q_share[1] - q_share[0]
+        batches = [qpool.submit(fpx.synth.make_queries, args.seed, 4242 + 1000003 * i, B, docs, H, query_len=args.query_len, first_query=q_share[0])
+                   for i in range(NQB)]
+    elif replica:
+        # (every rank its own queries: other targets, other noise)
+        B_global = B * world
+        batches = [qpool.submit(fpx.synth.make_queries, args.seed, 4242 + 1000003 * i + 7919 * rank, B, docs, H, query_len=args.query_len) for i in range(NQB)]
+    else:
+        batches = [qpool.submit(fpx.synth.make_queries, args.seed, 4242 + 1000003 * i, B, docs, H, query_len=args.query_len) for i in range(NQB)]
+
     t_build0 = time.perf_counter()
     segs, ranges = synth_index(fpx, ctx, args.seed, docs, S, H, set(local_segs), window=window)
     snapshot = fpx.Segments(ctx, segs)
@@ -629,26 +691,8 @@ def main():
     index_bytes = sum(s.device_bytes for s in segs if s.kind == "file")
     index_blocks = sum(s.num_blocks for s in segs if s.kind == "file")
 
-    # ---- queries (identical on every rank), resident in HBM before the timed region: NQB DISTINCT batches (different seeds,
-    #      different targets, different noise) that the steps rotate through, so that no step finds the previous step's
-    #      directory lines and pages in the caches / TLBs (a repeated batch is the TLB's best case)
-    NQB = max(1, int(os.environ.get("FPX_BENCH_QUERY_BATCHES", "8")))
-    opts = fpx.http_options(limit=args.limit, min_score=args.min_score)
-    # hash sharding, the ROUTED protocol (FPX_BENCH_ROUTED=0: round 3's, the whole batch's hashes on every rank): a rank holds only
-    # ITS share of the batch -- the queries it finishes -- and uploads nothing else
-    routed = shard_mode == "hash" and os.environ.get("FPX_BENCH_ROUTED", "1") != "0"
-    B_global = B
-    if routed:
-        bpr = fpx.shard_bins_per_rank(B_global, pw)
-        q_share = (min(B_global, rank * bpr * 8), min(B_global, (rank + 1) * bpr * 8))
-        B = q_share[1] - q_share[0]
-        batches = [fpx.synth.make_queries(args.seed, 4242 + 1000003 * i, B, docs, H, query_len=args.query_len, first_query=q_share[0]) for i in range(NQB)]
-    elif replica:
-        # (every rank its own queries: other targets, other noise)
-        B_global = B * world
-        batches = [fpx.synth.make_queries(args.seed, 4242 + 1000003 * i + 7919 * rank, B, docs, H, query_len=args.query_len) for i in range(NQB)]
-    else:
-        batches = [fpx.synth.make_queries(args.seed, 4242 + 1000003 * i, B, docs, H, query_len=args.query_len) for i in range(NQB)]
+    batches = [f.result() for f in batches]
+    qpool.shutdown()
     qbs = [fpx.QueryBatch(ctx, options=opts, flat=(f, o)) for f, o, _ in batches]
     flat, offsets, targets = batches[0]
     qb = qbs[0]
@@ -656,9 +700,9 @@ def main():
 
     agg = StatAgg()
 
-    import concurrent.futures as cf
     nfl = args.inflight if args.inflight > 0 else 3
     outs = [(np.zeros((B, cap, 2), np.uint32), np.zeros(B, np.uint32)) for _ in range(nfl)]
+    last_out = []                                      # (unsharded: the buffer the last step of run_steps wrote)
     if not sharded:
         shardeds = None
     elif routed:
@@ -678,16 +722,25 @@ def main():
         def which(i):
             return qbs[(first + i) % NQB] if rotate else qbs[0]
         if not sharded:
+            # every worker thread owns one of the `nfl` result buffers: a step never shares its buffer with another step in flight,
+            # and the buffer the last step wrote (last_out) holds that step's results when the pool is done
+            slots, mine = iter(range(nfl)), threading.local()
+
+            def own_slot():
+                mine.k = next(slots)
+
             def one(i):
-                o, n = outs[i % nfl]
+                o, n = outs[getattr(mine, "k", 0)]
                 _, _, st = fpx.search_resident(reader, which(i), 0, o, n)
                 if record:
                     agg.add(st)
+                if i == nsteps - 1:
+                    last_out[:] = [o, n]
             if nfl == 1:
                 for i in range(nsteps):
                     one(i)
             else:
-                with cf.ThreadPoolExecutor(nfl) as ex:
+                with cf.ThreadPoolExecutor(nfl, initializer=own_slot) as ex:
                     list(ex.map(one, range(nsteps)))
             return
 
@@ -801,13 +854,15 @@ def main():
     run_steps(args.steps, True)
     barrier()
     dt = time.perf_counter() - t0
-    out, out_n = outs[(args.steps - 1) % (4 if routed else nfl)]
+    out, out_n = outs[(args.steps - 1) % (4 if routed else nfl)] if sharded else last_out
     out, out_n = out.copy(), out_n.copy()
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, out, out_n)
     flat, offsets, targets = batches[(args.steps - 1) % NQB]          # (the batch of the last timed step: what `out` answers)
     qb = qbs[(args.steps - 1) % NQB]
     # the driver's K steps are few (20 x 0.9 ms): the same measurement over >= 200 steps, rotating and -- for comparison -- on ONE
     # repeated batch (what rounds 1-3 timed), both outside the contract's timed region
-    long_steps = max(200, args.steps) if not args.pmc_child and os.environ.get("FPX_BENCH_LONG", "1") != "0" else 0
+    long_steps = max(200, args.steps) if args.full and not args.pmc_child and os.environ.get("FPX_BENCH_LONG", "1") != "0" else 0
     dt_long = dt_rep = None
     if long_steps:
         barrier()
@@ -836,7 +891,7 @@ def main():
     top_scores = [int(out[q, 0, 1]) for q in range(q_lo, q_hi) if out_n[q] > 0]
 
     result = None
-    extras = rank == 0 and world == 1 and eworld <= 1 and not args.no_extras
+    extras = rank == 0 and world == 1 and eworld <= 1 and args.full and not args.no_extras
     if rank == 0:
         launches = max(1, int(agg.v["probe_launches"]))
         avg_ms = agg.v["probe_kernel_ms"] / launches
@@ -896,7 +951,7 @@ def main():
             "targets_found": found, "targets_total": q_hi - q_lo, "median_top_score": int(np.median(top_scores)) if top_scores else 0,
             "kernel_source_sha16": kernel_source_hash(),
         }
-        if not args.no_measure_bw:
+        if args.full and not args.no_measure_bw:
             s_gbs, r_gbs = ctx.measure_bandwidth(8 << 30, 512)
             result["measured_bandwidth"] = {"stream_read_GBs": s_gbs, "random_512B_read_GBs": r_gbs}
             # second denominator: what this box sustains for the kernel's own access pattern
@@ -1126,7 +1181,7 @@ def main():
         del pin_flats, pin_bufs
 
     # ---- CPU baseline on rank 0 at N = 1: the whole index in host RAM, pthread executor pool
-    if rank == 0 and world == 1 and eworld <= 1 and not args.no_cpu_baseline:
+    if rank == 0 and world == 1 and eworld <= 1 and args.full and not args.no_cpu_baseline:
         from oracle import oracle
         nq = min(args.cpu_queries, B)
         gpu_lists = fpx.results_to_lists(out[:nq], out_n[:nq])
@@ -1336,6 +1391,8 @@ def main():
         except OSError:
             pass
         sys.stdout.flush()
+        print(f"bench.py: {time.perf_counter() - t_main:.1f} s in main, the index built in {build_s:.1f} s, the timed steps {dt:.2f} s",
+              file=sys.stderr, flush=True)
         print(json.dumps(result), flush=True)
 
 

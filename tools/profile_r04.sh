@@ -13,7 +13,7 @@ R=$GRAFT_REPO_ROOT
 O=$R/gpurun_out/prof_r04
 rm -rf $O; mkdir -p $O
 cd /tmp && export TMPDIR=/tmp
-FPX_BENCH_PMC_KEEP=$O/pmc python $R/bench.py > $O/bench.json 2> $O/bench.err
+FPX_BENCH_PMC_KEEP=$O/pmc python $R/bench.py --full > $O/bench.json 2> $O/bench.err
 trace() {   # trace <tag> <out json> <cmd...>
   tag=$1; out=$2; shift 2
   rm -rf /tmp/tr_$tag
@@ -23,15 +23,15 @@ trace() {   # trace <tag> <out json> <cmd...>
   tail -c 2000 $O/trace_$tag.err > $O/trace_$tag.tail; rm -f $O/trace_$tag.err
   rm -rf /tmp/tr_$tag
 }
-trace r04 $O/bench_under_rocprof.json python $R/bench.py --no-cpu-baseline --no-extras --inflight 1
-FPX_DIRECT=0 trace r04b $O/bench_block_under_rocprof.json python $R/bench.py --no-cpu-baseline --no-extras --inflight 1 --steps 10
+trace r04 $O/bench_under_rocprof.json python $R/bench.py --full --no-cpu-baseline --no-extras --inflight 1
+FPX_DIRECT=0 trace r04b $O/bench_block_under_rocprof.json python $R/bench.py --full --no-cpu-baseline --no-extras --inflight 1 --steps 10
 FPX_BENCH_LONG=0 trace r04b1k $O/b1k.log python $R/tools/batch_trace.py 1024 30
 for n in 8 4 2; do
-  FPX_BENCH_EMULATE_WORLD=$n python $R/bench.py --no-cpu-baseline --no-extras > $O/emulated_rank_of_${n}_weak.json 2>> $O/emu.err
+  FPX_BENCH_EMULATE_WORLD=$n python $R/bench.py --full --no-cpu-baseline --no-extras > $O/emulated_rank_of_${n}_weak.json 2>> $O/emu.err
 done
-FPX_BENCH_EMULATE_WORLD=8 FPX_BENCH_SCALING=strong python $R/bench.py --no-cpu-baseline --no-extras > $O/emulated_rank_of_8_strong.json 2>> $O/emu.err
-FPX_BENCH_EMULATE_WORLD=8 FPX_BENCH_ROUTED=0 python $R/bench.py --no-cpu-baseline --no-extras > $O/emulated_rank_of_8_weak_replicated_hashes.json 2>> $O/emu.err
-FPX_BENCH_EMULATE_WORLD=8 FPX_BENCH_SETTLE_S=0 FPX_BENCH_LONG=0 trace r04emu $O/emulated_under_rocprof.json python $R/bench.py --no-cpu-baseline --no-extras --inflight 1
+FPX_BENCH_EMULATE_WORLD=8 FPX_BENCH_SCALING=strong python $R/bench.py --full --no-cpu-baseline --no-extras > $O/emulated_rank_of_8_strong.json 2>> $O/emu.err
+FPX_BENCH_EMULATE_WORLD=8 FPX_BENCH_ROUTED=0 python $R/bench.py --full --no-cpu-baseline --no-extras > $O/emulated_rank_of_8_weak_replicated_hashes.json 2>> $O/emu.err
+FPX_BENCH_EMULATE_WORLD=8 FPX_BENCH_SETTLE_S=0 FPX_BENCH_LONG=0 trace r04emu $O/emulated_under_rocprof.json python $R/bench.py --full --no-cpu-baseline --no-extras --inflight 1
 tail -c 3000 $O/emu.err > $O/emu.tail; rm -f $O/emu.err
 python $R/tools/merge_then_search.py > $O/merge_then_search.json 2> $O/mts.err; tail -c 1000 $O/mts.err > $O/mts.tail; rm -f $O/mts.err
 python3 $R/tools/brief.py $O/bench.json $O/bench_under_rocprof.json $O/emulated_rank_of_8_weak.json $O/emulated_rank_of_4_weak.json $O/emulated_rank_of_2_weak.json $O/emulated_rank_of_8_strong.json $O/emulated_rank_of_8_weak_replicated_hashes.json

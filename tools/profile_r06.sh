@@ -14,7 +14,7 @@ R=$GRAFT_REPO_ROOT
 O=$R/gpurun_out/prof_r06
 rm -rf $O; mkdir -p $O
 cd /tmp && export TMPDIR=/tmp
-FPX_BENCH_PMC_KEEP=$O/pmc python $R/bench.py > $O/bench.json 2> $O/bench.err
+FPX_BENCH_PMC_KEEP=$O/pmc python $R/bench.py --full > $O/bench.json 2> $O/bench.err
 trace() {   # trace <tag> <out json> <cmd...>
   tag=$1; out=$2; shift 2
   rm -rf /tmp/tr_$tag
@@ -24,12 +24,12 @@ trace() {   # trace <tag> <out json> <cmd...>
   tail -c 2000 $O/trace_$tag.err > $O/trace_$tag.tail; rm -f $O/trace_$tag.err
   rm -rf /tmp/tr_$tag
 }
-trace r06 $O/bench_under_rocprof.json python $R/bench.py --no-cpu-baseline --no-extras --inflight 1
-FPX_DIRECT=0 trace r06b $O/bench_block_under_rocprof.json python $R/bench.py --no-cpu-baseline --no-extras --inflight 1 --steps 10
+trace r06 $O/bench_under_rocprof.json python $R/bench.py --full --no-cpu-baseline --no-extras --inflight 1
+FPX_DIRECT=0 trace r06b $O/bench_block_under_rocprof.json python $R/bench.py --full --no-cpu-baseline --no-extras --inflight 1 --steps 10
 FPX_BENCH_LONG=0 trace r06b1k $O/b1k.log python $R/tools/batch_trace.py 1024 30
-FPX_BENCH_EMULATE_WORLD=8 python $R/bench.py --no-cpu-baseline --no-extras > $O/emulated_rank_of_8_weak.json 2>> $O/emu.err
+FPX_BENCH_EMULATE_WORLD=8 python $R/bench.py --full --no-cpu-baseline --no-extras > $O/emulated_rank_of_8_weak.json 2>> $O/emu.err
 # the pipeline (keys - probe - bins - score) on the same index, for the record: query_wg 0
-FPX_QUERY_WG=0 FPX_BENCH_LONG=0 trace r06pipe $O/bench_pipeline_under_rocprof.json python $R/bench.py --no-cpu-baseline --no-extras --inflight 1
+FPX_QUERY_WG=0 FPX_BENCH_LONG=0 trace r06pipe $O/bench_pipeline_under_rocprof.json python $R/bench.py --full --no-cpu-baseline --no-extras --inflight 1
 tail -c 3000 $O/emu.err > $O/emu.tail; rm -f $O/emu.err
 
 # a live index's snapshot shapes (tools/live_index.py) and the kernels of the fullest one; two replicas sharing this one GPU (the N > 1 default, flow only)
