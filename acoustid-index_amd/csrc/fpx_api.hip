@@ -420,7 +420,7 @@ static const OptInfo OPT_TABLE[OPT_COUNT] = {
     /* OPT_LEAN_MIN */           {"lean_min", "FPX_LEAN_MIN", 1ll << 16, 0, true},
     /* OPT_SHARDED_WORKERS */    {"sharded_workers", "FPX_SHARDED_WORKERS", 3, 1, true},
     /* OPT_HOT_REFS */           {"hot_refs", "FPX_HOT_REFS", -1, -1, true},                     // 1 | 0 | -1: hot lists reach the score kernel by reference | are copied | by the last batch's records
-    /* OPT_QUERY_WG */           {"query_wg", "FPX_QUERY_WG", 1, 0, false},                      // 1 | 0: a snapshot that is ONE packed group is searched a query per workgroup (fpx_qsearch.hpp) | by the keys - probe - bins - score pipeline
+    /* OPT_QUERY_WG */           {"query_wg", "FPX_QUERY_WG", 1, 0, false},                      // 1 | 0 | 2: a snapshot that is ONE packed group is searched a query per workgroup (fpx_qsearch.hpp) | by the keys - probe - bins - score pipeline | as 1, a group with superseded docs or masked columns too
 };
 
 int64_t ctx_opt(const Ctx* c, CtxOpt o)
@@ -1028,13 +1028,18 @@ int fpx_snapshot_create(fpx_ctx* ctx_, fpx_segment* const* segs, uint32_t num_se
     // few; k_merge (fpx_score.hpp) puts the two tables together under the queries' relative cut-off.  search_batch_impl decides per batch.
     // (several groups -- a merge's results met in a snapshot and formed one of their own: part 0 is the LARGEST packed group that is whole
     // here, every column searched and no doc of it superseded; the other groups go with part 1)
+    // Under query_wg 2 -- the value in force when the snapshot is made -- part 0 may also be a group with superseded docs or columns outside
+    // the snapshot (k_search_query's filtered instantiation).  Its dead sets hold the docs of part 1's segments and of the memory segments
+    // as well: they are docs-only members of part 0 (snapshot_build: compute_dead runs over the whole segment list).
     int g0 = -1;
     uint64_t g0_items = 0;
-    if (ctx_opt(c, OPT_QUERY_WG) != 0 && (sn->n_file != 0 || sn->n_solo != 0 || sn->n_group > 1)) {
+    const int64_t query_wg = ctx_opt(c, OPT_QUERY_WG);
+    if (query_wg != 0 && (sn->n_file != 0 || sn->n_solo != 0 || sn->n_group > 1)) {
         for (uint32_t gi = 0; gi < sn->n_group; ++gi) {
             const GroupDesc& gd = sn->h_group[gi];
             const Group* g = sn->groups[gi].get();
-            if (!g->packed || gd.any_dead != 0u || gd.active != (gd.nseg >= 32u ? 0xFFFFFFFFu : ((1u << gd.nseg) - 1u))) continue;
+            if (!g->packed) continue;
+            if (query_wg != 2 && (gd.any_dead != 0u || gd.active != (gd.nseg >= 32u ? 0xFFFFFFFFu : ((1u << gd.nseg) - 1u)))) continue;
             uint64_t items = 0;
             for (const Segment* s : sn->segs) if (s->kind == 0 && s->ctx == c && s->home == sn->groups[gi]) items += s->num_items;
             if (g0 < 0 || items > g0_items) { g0 = (int)gi; g0_items = items; }

@@ -16,6 +16,9 @@
 // Taken by run_batch for snapshots that are ONE packed group and nothing else (the resident index between merges), every column searched,
 // no superseded docs, queries of up to QS_MAX_HASHES hashes with a floor above 2; a query whose records outgrow the LDS array (hot
 // hashes: hundreds of docs per list) fails the batch over to the pipeline above (CTR_BINFAIL), which stays the path for everything else.
+// FILT (option query_wg = 2): the same for a group with superseded docs and/or columns outside the snapshot (a live index between a
+// merge and its regroup) -- every word knows its column, as in k_probe_pgroup's per-column walk: a column outside `active` gives no
+// record and no statistic, a doc of a column with a dead set is dropped after it was counted (CTR_DOCS counts before supersession).
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -51,6 +54,7 @@ constexpr uint32_t QS_WORDS = FPX_QS_WORDS;                  // words of a hash 
 constexpr uint32_t QS_CH = FPX_QS_CH;                      // rounds whose line heads are under way together
 constexpr uint32_t QS_TASKS = (((size_t)2u << QS_FLOG2) + ((size_t)8u << QS_TLOG2)) / 8u;      // deferred lists / words of a query (8 bytes each: they live where the filter and the exact table will)
 constexpr uint32_t QS_TASK_WORDS = 8;              // words a deferred "words" task carries at most (a list's task: its header + seven docs)
+constexpr uint32_t QS_TASKS_FILT = QS_TASKS * 8u / 12u;      // (FILT) the same bytes hold fewer tasks: each has a word of its words' columns behind the queue
 static_assert(QS_MAX_HASHES * 2u <= QS_REC_CAP, "the dedup set lives where the records will");
 static_assert((QS_MAX_HASHES + QS_WG - 1u) / QS_WG <= QS_MAX_ROUNDS, "rounds per query");
 static_assert(QS_WORDS % 4 == 0 && QS_WORDS <= 16, "the words are fetched in 16-byte pieces; a lane's masks of them are 16 bits");
@@ -96,7 +100,8 @@ __device__ __forceinline__ uint3 gload_u3(const uint32_t* p)            // the f
 __device__ __forceinline__ uint32_t qs_cell(uint32_t doc) { return (doc ^ (doc >> QS_FLOG2)) & ((1u << QS_FLOG2) - 1u); }
 // a deferred task: the address of a list, or of up to eight words of a hash that its lane did not walk (beyond its own, or overflowed from
 // the line into `ext`) -- bits 0..45: address >> 2, 46..48: words - 1, 49..56: which of them are second words of doubles, 57..62: the
-// hash's chunk (a list reference among the words counts from the chunk's `ext`), 63: a list
+// hash's chunk (a list reference among the words counts from the chunk's `ext`), 63: a list.  (FILT: a list's column in bits 46..49; a
+// words task's columns -- word j in bits 4j .. 4j+3 -- in a parallel array behind the queue)
 __device__ __forceinline__ unsigned long long qs_task_list(const uint32_t* p, uint32_t chunk)
 {
     return ((unsigned long long)p >> 2) | ((unsigned long long)chunk << 57) | (1ull << 63);
@@ -106,6 +111,18 @@ __device__ __forceinline__ unsigned long long qs_task_words(const uint32_t* p, u
     return ((unsigned long long)p >> 2) | ((unsigned long long)(cnt - 1u) << 46) | ((unsigned long long)(second & 0xFFu) << 49) | ((unsigned long long)chunk << 57);
 }
 __device__ __forceinline__ const uint32_t* qs_task_ptr(unsigned long long e) { return reinterpret_cast<const uint32_t*>((e & ((1ull << 46) - 1ull)) << 2); }
+// (FILT) the columns of words j0 .. j0 + cnt - 1 of a hash (cnt <= 8) -- its columns pm ascending, a double (dm) two words of one --, word
+// j0 + t in bits 4t .. 4t+3
+__device__ __forceinline__ uint32_t qs_word_cols(uint32_t pm, uint32_t dm, uint32_t j0, uint32_t cnt)
+{
+    uint32_t cols = 0, rest = pm, i = 0, w = 0;
+    while (rest != 0u && w < j0 + cnt) {
+        const uint32_t s = (uint32_t)__builtin_ctz(rest), span = 1u + ((dm >> i) & 1u);
+        for (uint32_t t = 0; t < span; ++t, ++w) if (w >= j0 && w < j0 + cnt) cols |= s << (4u * (w - j0));
+        ++i; rest &= rest - 1u;
+    }
+    return cols;
+}
 
 // (FPX_QS_PROF: an experiment build -- wave 0 of every workgroup adds the clocks it spent between the kernel's phases to the batch's
 // counters [16 ..], which the host prints; tools/build_variant.sh qs_prof -DFPX_QS_PROF=1)
@@ -114,8 +131,9 @@ __device__ __forceinline__ const uint32_t* qs_task_ptr(unsigned long long e) { r
 #else
 #define QS_MARK(i) do { } while (0)
 #endif
-// (MEM: the snapshot has memory segments -- an instantiation of its own: their look-up costs the usual one registers)
-template <int NS, bool QS, bool MEM>
+// (MEM: the snapshot has memory segments -- an instantiation of its own: their look-up costs the usual one registers.  FILT: the group has
+// superseded docs and/or columns outside the snapshot -- the supersession filter and the column masks, ga.segs' dead sets)
+template <int NS, bool QS, bool MEM, bool FILT>
 __global__ __launch_bounds__(QS_WG) FPX_QS_OCC void k_search_query(QSearchArgs a, GroupArgs ga)
 {
 #ifdef FPX_QS_PROF
@@ -128,6 +146,8 @@ __global__ __launch_bounds__(QS_WG) FPX_QS_OCC void k_search_query(QSearchArgs a
     uint32_t* const filter = recs + QS_REC_CAP + 4u;                                                    // 2^(QS_FLOG2 - 1) words of two cells
     unsigned long long* const table = reinterpret_cast<unsigned long long*>(filter + (1u << (QS_FLOG2 - 1u)));
     unsigned long long* const tasks = reinterpret_cast<unsigned long long*>(filter);                   // (until the records are complete)
+    constexpr uint32_t TCAP = FILT ? QS_TASKS_FILT : QS_TASKS;                                          // tasks the queue holds
+    uint32_t* const tcols = reinterpret_cast<uint32_t*>(tasks + QS_TASKS_FILT);                         // (FILT) [TCAP] a words task's columns
     uint64_t* const cbuf = reinterpret_cast<uint64_t*>(table + T);                                      // [SB_CAND]
     __shared__ uint32_t s_count, s_ntask, s_over_recs, s_seen_ones, s_cancel, s_claimed, s_full, s_ccnt, s_cshared, s_cbase_lo, s_cbase_hi;
     __shared__ unsigned long long wg_blocks, wg_docs, wg_probes, wg_reads;
@@ -135,6 +155,7 @@ __global__ __launch_bounds__(QS_WG) FPX_QS_OCC void k_search_query(QSearchArgs a
     __shared__ uint32_t s_first[FUSE_MAX], s_last[FUSE_MAX];
     __shared__ const uint32_t* s_ext[GROUP_CHUNKS];
     __shared__ uint32_t s_q2;                           // the query after the next one (handed out by the launch's counter)
+    __shared__ uint32_t s_dseg[FUSE_MAX];               // (FILT) a column's descriptor in ga.segs where it has superseded docs, else ~0
 
     const uint32_t tid = threadIdx.x, lane = tid & 63u;
     const GroupDesc* g = &ga.g;
@@ -148,6 +169,7 @@ __global__ __launch_bounds__(QS_WG) FPX_QS_OCC void k_search_query(QSearchArgs a
     const uint32_t* qh = a.hashes_base + q_lo;
     if (tid < FUSE_MAX) { s_first[tid] = g->first_hash[tid]; s_last[tid] = g->last_hash[tid]; }
     if (tid < GROUP_CHUNKS) s_ext[tid] = tid < g->nchunks ? g->ext_tab[tid] : nullptr;
+    if (FILT && tid < FUSE_MAX) s_dseg[tid] = g->has_dead[tid] != 0u ? g->seg_index[tid] : 0xFFFFFFFFu;
     // ---- the first QS_CH rounds' hashes and the heads of their lines (position bits, double flags) set out at once: a round is a chain
     //      of latencies -- hash, line head (HBM), words, ... -- and a CU holds sixteen waves to overlap them; what does not depend on the
     //      round before it is asked for up front.  (A duplicate's line is fetched for nothing: dedup runs while the heads travel.)
@@ -242,6 +264,11 @@ __global__ __launch_bounds__(QS_WG) FPX_QS_OCC void k_search_query(QSearchArgs a
 
     const uint32_t active = g->active, nactive = (uint32_t)__popc(active);
     uint32_t my_blocks = 0, my_docs = 0, my_probes = 0, my_reads = 0;
+    // (FILT) a doc of column s that a newer segment supersedes (src/common.zig:158; the column's dead set, k_probe_pgroup's test)
+    auto dead_in = [&](uint32_t s, uint32_t doc) -> bool {
+        const uint32_t di = s_dseg[s];
+        return di != 0xFFFFFFFFu && is_dead_seg(ga.segs[di], doc);
+    };
     // ---- records.  `n` docs of the lane (mask km over d[]) join the query's array: one reservation per wave -- a scan on the DPP
     //      crossbar: the whole wave is here (fpx_pgroup.hpp x5) --, doc j at pos + (docs of the lane before it); a slot without a doc
     //      writes the sink word behind the array (no branch per slot).  The filter is counted later, over the array (every lane busy).
@@ -285,7 +312,7 @@ __global__ __launch_bounds__(QS_WG) FPX_QS_OCC void k_search_query(QSearchArgs a
     // a task joins the queue (a full queue: the batch goes the long way)
     auto push_task = [&](unsigned long long e) {
         const uint32_t at = atomicAdd(&s_ntask, 1u);
-        if (at < QS_TASKS) tasks[at] = e; else s_over_recs = 1u;
+        if (at < TCAP) tasks[at] = e; else s_over_recs = 1u;
     };
 
     // ---- FileSegment.search for every column, a hash per lane and round (fpx_pgroup.hpp: the line's layout)
@@ -345,10 +372,33 @@ __global__ __launch_bounds__(QS_WG) FPX_QS_OCC void k_search_query(QSearchArgs a
             lmask |= (v && neg && word != 0xFFFFFFFFu) ? (1u << j) : 0u;        // a list reference
             gw[j] = neg ? word : g->gmin + word;
         }
+        // (FILT) the walked words by their column (k_probe_pgroup's walk, a column's one or two words at a time): words of a column outside
+        // the snapshot are nothing; dmask: the words whose column has superseded docs.  (A word's own column, where it is needed -- a
+        // doc of such a column, a list reference --, is walked to again: no register holds the twelve)
+        uint32_t dmask = 0;
+        if constexpr (FILT) {
+            uint32_t amask = 0;
+            for (uint32_t r = pm, i = 0, w = 0; r != 0u && w < mine; r &= r - 1u, ++i) {
+                const uint32_t s = (uint32_t)__builtin_ctz(r), span = 1u + ((dm >> i) & 1u), bits = ((1u << span) - 1u) << w;
+                amask |= ((active >> s) & 1u) != 0u ? bits : 0u;
+                dmask |= s_dseg[s] != 0xFFFFFFFFu ? bits : 0u;
+                w += span;
+            }
+            keep &= amask; lmask &= amask;
+        }
         my_docs += (uint32_t)__popc(keep);
         my_blocks += (uint32_t)__popc(keep & ~second);
         // (the scan histograms: a double is ONE observation of two docs, counted where its second word is -- the upper half of my_probes)
         if constexpr (SCAN_HIST && (FPX_SH_BITS & 2)) my_probes += (uint32_t)__popc(keep & second) << 16;
+        if constexpr (FILT) {                                                   // (counted above: CTR_DOCS counts before supersession)
+            for (uint32_t m = keep & dmask; m != 0u; m &= m - 1u) {
+                const uint32_t j0 = (uint32_t)__builtin_ctz(m);
+                uint32_t doc = 0;
+#pragma unroll
+                for (uint32_t j = 0; j < QS_WORDS; ++j) doc = j == j0 ? gw[j] : doc;
+                if (dead_in(qs_word_cols(pm, dm, j0, 1u), doc)) keep &= ~(1u << j0);
+            }
+        }
         emit(keep, gw);
         // ---- what the round does not wait for joins the query's task queue -- the hash's lists (their heads are other lines: HBM), its
         //      words beyond the lane's own and those that overflowed the line into `ext` --; the workgroup takes the tasks up together
@@ -360,8 +410,12 @@ __global__ __launch_bounds__(QS_WG) FPX_QS_OCC void k_search_query(QSearchArgs a
         const uint32_t nt = (uint32_t)__popc(lmask) + (in_line + QS_TASK_WORDS - 1u) / QS_TASK_WORDS + (in_ext + QS_TASK_WORDS - 1u) / QS_TASK_WORDS;
         uint32_t tat = reserve_in(&s_ntask, nt);
         if (nt != 0u) {
-            if (tat + nt > QS_TASKS) { s_over_recs = 1u; tat = QS_TASKS; }        // (a full queue: the batch goes the long way)
-            auto put_task = [&](unsigned long long e) { if (tat < QS_TASKS) tasks[tat] = e; ++tat; };
+            if (tat + nt > TCAP) { s_over_recs = 1u; tat = TCAP; }                // (a full queue: the batch goes the long way)
+            auto put_task = [&](unsigned long long e) { if (tat < TCAP) tasks[tat] = e; ++tat; };
+            auto put_words = [&](unsigned long long e, uint32_t j0, uint32_t c) {
+                if constexpr (FILT) { if (tat < TCAP) tcols[tat] = qs_word_cols(pm, dm, j0, c); }
+                put_task(e);
+            };
             const uint32_t chunk = (h >> GROUP_CHUNK_LOG2) - g->chunk0;
             const uint32_t* ext = s_ext[chunk];
             uint32_t lm = lmask;
@@ -371,13 +425,13 @@ __global__ __launch_bounds__(QS_WG) FPX_QS_OCC void k_search_query(QSearchArgs a
                 uint32_t e = 0;
 #pragma unroll
                 for (uint32_t j = 0; j < QS_WORDS; ++j) e = j == j0 ? gw[j] : e;
-                put_task(qs_task_list(ext + (e & 0x7FFFFFFFu), chunk));
+                put_task(qs_task_list(ext + (e & 0x7FFFFFFFu), chunk) | (FILT ? ((unsigned long long)qs_word_cols(pm, dm, j0, 1u) << 46) : 0ull));
             }
             uint32_t j = mine;
             // ... words still in the line (the hash has more than the lane walks)
             while (j < mine + in_line) {
                 const uint32_t c = min(mine + in_line - j, QS_TASK_WORDS);
-                put_task(qs_task_words(line_of(h) + 3u + start + j, c, second >> j, chunk));
+                put_words(qs_task_words(line_of(h) + 3u + start + j, c, second >> j, chunk), j, c);
                 j += c;
             }
             // ... and behind its end, in `ext` at the offset the line's last word holds
@@ -385,7 +439,7 @@ __global__ __launch_bounds__(QS_WG) FPX_QS_OCC void k_search_query(QSearchArgs a
                 const uint32_t* ob = ext + gload_u32(line_of(h) + (GROUP_LINE_WORDS - 1u));
                 while (j < nwords) {                     // (start + j >= inl here)
                     const uint32_t c = min(nwords - j, QS_TASK_WORDS);
-                    put_task(qs_task_words(ob + (start + j - inl), c, second >> j, chunk));
+                    put_words(qs_task_words(ob + (start + j - inl), c, second >> j, chunk), j, c);
                     j += c;
                 }
                 my_reads += 2u;
@@ -453,7 +507,7 @@ __global__ __launch_bounds__(QS_WG) FPX_QS_OCC void k_search_query(QSearchArgs a
     {
         uint32_t t_lo = 0;
         for (;;) {
-            const uint32_t t_hi = min(s_ntask, QS_TASKS);                        // (uniform: read behind a barrier ...
+            const uint32_t t_hi = min(s_ntask, TCAP);                            // (uniform: read behind a barrier ...
             __syncthreads();                                                      // ... and nobody pushes before everybody has read it)
             if (t_lo >= t_hi) break;
             for (uint32_t t0 = t_lo; t0 < t_hi; t0 += QS_WG) {
@@ -461,6 +515,9 @@ __global__ __launch_bounds__(QS_WG) FPX_QS_OCC void k_search_query(QSearchArgs a
                 const unsigned long long e = has ? tasks[t0 + tid] : 0ull;
                 const bool is_list = has && (e >> 63) != 0ull;
                 const uint32_t* p = qs_task_ptr(e);
+                // (FILT) a list's column; a words task's columns
+                const uint32_t lcol = FILT ? (uint32_t)(e >> 46) & 15u : 0u;
+                const uint32_t tc = (FILT && has && !is_list) ? tcols[t0 + tid] : 0u;
                 uint32_t d[QS_TASK_WORDS];
 #pragma unroll
                 for (uint32_t j = 0; j < QS_TASK_WORDS; ++j) d[j] = 0xFFFFFFFFu;
@@ -489,7 +546,7 @@ __global__ __launch_bounds__(QS_WG) FPX_QS_OCC void k_search_query(QSearchArgs a
                     const uint32_t second = (uint32_t)(e >> 49) & 0xFFu;
 #pragma unroll
                     for (uint32_t j = 0; j < QS_TASK_WORDS; ++j) {
-                        const bool v = j < cnt, neg = (int32_t)d[j] < 0;
+                        const bool v = j < cnt && (!FILT || ((active >> ((tc >> (4u * j)) & 15u)) & 1u) != 0u), neg = (int32_t)d[j] < 0;
                         km |= (v && !neg) ? (1u << j) : 0u;
                         lm |= (v && neg && d[j] != 0xFFFFFFFFu) ? (1u << j) : 0u;
                     }
@@ -498,6 +555,17 @@ __global__ __launch_bounds__(QS_WG) FPX_QS_OCC void k_search_query(QSearchArgs a
                 }
 #pragma unroll
                 for (uint32_t j = 0; j < QS_TASK_WORDS; ++j) d[j] = ((int32_t)d[j] < 0 && !is_list) ? d[j] : g->gmin + d[j];
+                if constexpr (FILT) {                   // (counted above: before supersession)
+                    for (uint32_t m = km; m != 0u; m &= m - 1u) {
+                        const uint32_t j0 = (uint32_t)__builtin_ctz(m);
+                        const uint32_t s = is_list ? lcol : (tc >> (4u * j0)) & 15u;
+                        if (s_dseg[s] == 0xFFFFFFFFu) continue;
+                        uint32_t doc = 0;
+#pragma unroll
+                        for (uint32_t j = 0; j < QS_TASK_WORDS; ++j) doc = j == j0 ? d[j] : doc;
+                        if (dead_in(s, doc)) km &= ~(1u << j0);
+                    }
+                }
                 emit(km, d);
                 while (lm != 0u) {                      // (a list inside the words: the next pass's)
                     const uint32_t j0 = (uint32_t)__builtin_ctz(lm);
@@ -506,7 +574,7 @@ __global__ __launch_bounds__(QS_WG) FPX_QS_OCC void k_search_query(QSearchArgs a
 #pragma unroll
                     for (uint32_t j = 0; j < QS_TASK_WORDS; ++j) w = j == j0 ? d[j] : w;
                     const uint32_t chunk = (uint32_t)(e >> 57) & 63u;
-                    push_task(qs_task_list(s_ext[chunk] + (w & 0x7FFFFFFFu), chunk));
+                    push_task(qs_task_list(s_ext[chunk] + (w & 0x7FFFFFFFu), chunk) | (FILT ? ((unsigned long long)((tc >> (4u * j0)) & 15u) << 46) : 0ull));
                 }
                 // lists longer than their head: the wave reads them on, 64 docs at a time
                 unsigned long long ml = __ballot((int)long_list);
@@ -515,9 +583,11 @@ __global__ __launch_bounds__(QS_WG) FPX_QS_OCC void k_search_query(QSearchArgs a
                     ml &= ml - 1ull;
                     const uint32_t* list = reinterpret_cast<const uint32_t*>(((uint64_t)__shfl((uint32_t)((uint64_t)p >> 32), src) << 32) | __shfl((uint32_t)(uint64_t)p, src));
                     const uint32_t eff_s = __shfl(eff, src), T_s = __shfl(Tl, src), from = __shfl(xin, src);
+                    const uint32_t col_s = FILT ? (uint32_t)__shfl(lcol, src) : 0u;
                     for (uint32_t o2 = from; o2 < eff_s; o2 += 64u) {
-                        const bool kp = o2 + lane < eff_s;
+                        bool kp = o2 + lane < eff_s;
                         const uint32_t dv = g->gmin + (kp ? gload_u32(list + 1u + T_s + o2 + lane) : 0u);
+                        if constexpr (FILT) { if (kp) kp = !dead_in(col_s, dv); }
                         emit1(kp, dv);
                     }
                 }

@@ -449,11 +449,14 @@ static int run_batch(Snapshot* snap, Workspace* ws, const QueryBatch* resident, 
     //      superseded docs -- the resident index between merges --, the queries short enough for their hash set and their floor above the
     //      legacy protocol's: dedup, probe, count and floor happen in ONE kernel, no keys are made or ordered, no record reaches HBM.
     //      Anything else, and a batch that kernel hands back (hot hashes: a query's records outgrow its LDS array), runs the pipeline below.
-    bool qs_path = false;
+    //      Option query_wg 2: a group with superseded docs or columns outside the snapshot too, by the kernel's filtered instantiation (qs_filt).
+    bool qs_path = false, qs_filt = false;
+    const int64_t query_wg = ctx_opt(snap->ctx, OPT_QUERY_WG);
     if (!ex && !no_fast && !no_qs && !single_fast && B >= 2u && P != 0 && qb <= 24u && snap->n_file == 0 && snap->n_solo == 0 && snap->n_group == 1 &&
-        snap->n_direct != 0 && (snap->n_mem == 0 || snap->mem_items == 0 || snap->d_memtab != nullptr) && snap->groups[0]->packed && ctx_opt(snap->ctx, OPT_QUERY_WG) != 0) {
+        snap->n_direct != 0 && (snap->n_mem == 0 || snap->mem_items == 0 || snap->d_memtab != nullptr) && snap->groups[0]->packed && query_wg != 0) {
         const GroupDesc& gd = snap->h_group[0];
-        qs_path = gd.any_dead == 0u && gd.active == (gd.nseg >= 32u ? 0xFFFFFFFFu : ((1u << gd.nseg) - 1u));
+        qs_filt = gd.any_dead != 0u || gd.active != (gd.nseg >= 32u ? 0xFFFFFFFFu : ((1u << gd.nseg) - 1u));
+        qs_path = !qs_filt || query_wg == 2;
         for (uint32_t q = 0; q < B && qs_path; ++q) {
             const uint64_t raw_len = offsets[q + 1] - offsets[q];
             qs_path = raw_len <= QS_MAX_HASHES && (opts[q].has_min_score ? opts[q].min_score : (uint32_t)((raw_len + 19) / 20)) > 2u;
@@ -669,12 +672,20 @@ static int run_batch(Snapshot* snap, Workspace* ws, const QueryBatch* resident, 
             const dim3 qgrid(std::min<uint32_t>(qa.q_end - qa.q_begin, (uint32_t)cus * QS_WGS_PER_CU));
             const bool mem = qa.mem_tab != nullptr;
             auto launch = [&](auto kernel) { hipLaunchKernelGGL(kernel, qgrid, dim3(QS_WG), QS_LDS_BYTES, st, qa, gargs); };
-            if (grp->ns == 8u) {
-                if (mem) { if (want_q) launch(k_search_query<8, true, true>); else launch(k_search_query<8, false, true>); }
-                else { if (want_q) launch(k_search_query<8, true, false>); else launch(k_search_query<8, false, false>); }
+            if (qs_filt) {
+                if (grp->ns == 8u) {
+                    if (mem) { if (want_q) launch(k_search_query<8, true, true, true>); else launch(k_search_query<8, false, true, true>); }
+                    else { if (want_q) launch(k_search_query<8, true, false, true>); else launch(k_search_query<8, false, false, true>); }
+                } else {
+                    if (mem) { if (want_q) launch(k_search_query<16, true, true, true>); else launch(k_search_query<16, false, true, true>); }
+                    else { if (want_q) launch(k_search_query<16, true, false, true>); else launch(k_search_query<16, false, false, true>); }
+                }
+            } else if (grp->ns == 8u) {
+                if (mem) { if (want_q) launch(k_search_query<8, true, true, false>); else launch(k_search_query<8, false, true, false>); }
+                else { if (want_q) launch(k_search_query<8, true, false, false>); else launch(k_search_query<8, false, false, false>); }
             } else {
-                if (mem) { if (want_q) launch(k_search_query<16, true, true>); else launch(k_search_query<16, false, true>); }
-                else { if (want_q) launch(k_search_query<16, true, false>); else launch(k_search_query<16, false, false>); }
+                if (mem) { if (want_q) launch(k_search_query<16, true, true, false>); else launch(k_search_query<16, false, true, false>); }
+                else { if (want_q) launch(k_search_query<16, true, false, false>); else launch(k_search_query<16, false, false, false>); }
             }
             if (up_chunks && c + 1u < up_chunks && (rc = upload_piece(c + 1u))) return rc;       // (the next piece crosses PCIe under this kernel)
         }
@@ -740,7 +751,7 @@ static int run_batch(Snapshot* snap, Workspace* ws, const QueryBatch* resident, 
             stats->probe_kernel_ms += ms; stats->total_gpu_ms += total_ms; stats->probe_launches += 1;
             stats->probe_kernel_bytes += blocks * 512ull + bytes_off;
             stats->probe_kernel_fetched_bytes += (dreads + 1) / 2 * 128ull;
-            stats->path_flags |= 1u | (Cf ? 2u : 0u) | 4u | 64u;
+            stats->path_flags |= 1u | (Cf ? 2u : 0u) | 4u | 64u | (qs_filt ? 256u : 0u);
         }
         if ((rc = deliver_qstats())) return rc;
         ws->hint_P = P; ws->hint_H = std::max<uint64_t>(records, 1);          // (sizes the pipeline's bins should a later batch take it)
@@ -1455,10 +1466,16 @@ static void add_stats(fpx_stats* dst, const fpx_stats& s)
 
 // one pass, or -- when (query index, score) do not fit the 64-bit candidate key -- two half batches
 // would part 0 of the snapshot run this batch a query per workgroup?  (run_batch's own test for it, on the host arrays; a batch it would
-// not take gains nothing from two parts)
+// not take gains nothing from two parts.  A part 0 whose group has superseded docs or masked columns -- made under query_wg 2 -- only
+// while the option is 2)
 static bool parts_take(const Snapshot* snap, const uint64_t* offsets, const fpx_opts* opts, uint32_t B)
 {
-    if (ctx_opt(snap->ctx, OPT_QUERY_WG) == 0) return false;
+    const int64_t query_wg = ctx_opt(snap->ctx, OPT_QUERY_WG);
+    if (query_wg == 0) return false;
+    if (query_wg != 2) {
+        const GroupDesc& gd = snap->part[0]->h_group[0];
+        if (gd.any_dead != 0u || gd.active != (gd.nseg >= 32u ? 0xFFFFFFFFu : ((1u << gd.nseg) - 1u))) return false;
+    }
     if (bits_for(B) > 24u || offsets[B] == offsets[0]) return false;
     for (uint32_t q = 0; q < B; ++q) {
         const uint64_t raw_len = offsets[q + 1] - offsets[q];

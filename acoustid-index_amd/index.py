@@ -53,7 +53,9 @@ class Context:
 
     def set_option(self, name, value):
         """fpx_ctx_set_option: any option of include/fpx.h ('direct', 'fuse_min', 'binned', 'fast', 'rec32', ...); a value below the
-        option's smallest (-1, or -2 for 'group_packed' / 'bin_q_log2') puts it back to the environment / default"""
+        option's smallest (-1, or -2 for 'group_packed' / 'bin_q_log2') puts it back to the environment / default.  'query_wg': 1 | 0 | 2
+        -- a snapshot that is one packed group searched a query per workgroup | by the pipeline | as 1, a group with superseded docs or
+        masked columns too (Stats.path_flags bit 8)"""
         check(lib().fpx_ctx_set_option(self.h, name.encode(), int(value)))
 
     def trim(self):

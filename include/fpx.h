@@ -83,7 +83,9 @@ typedef struct {
                                    bit 6: the batch was searched a query per workgroup (k_search_query: no keys, no bins),
                                    bit 7: the snapshot was searched in TWO PARTS -- its one packed group (+ the memory segments) a query
                                    per workgroup, the file segments next to it by the pipeline, the two tables merged (a live index
-                                   between merges: fpx_snapshot_create) */
+                                   between merges: fpx_snapshot_create),
+                                   bit 8: the batch (or its part 0) ran the FILTERED k_search_query: a packed group with superseded
+                                   docs and/or columns outside the snapshot, searched a query per workgroup ("query_wg" 2) */
     uint64_t probe_kernel_fetched_bytes; /* block bytes the main probe kernel really fetched, in 128-byte lines: a probe
                                    whose hash the segment's presence bits know to be absent counts as a visited block (as in
                                    the reference) without the block being read, and a block that is read costs two lines up
@@ -109,9 +111,11 @@ int  fpx_ctx_device(const fpx_ctx *ctx);     /* the HIP ordinal the context live
  *   "presence_min_items" items from which a segment in blocks gets presence bits and probe records (the lean kernel; default 2^20)
  *   "lean_head"          4: the lean kernel always fetches whole blocks (default 0: two lines where a block's head fits them)
  * Search paths -- read per batch:
- *   "query_wg"           1 | 0   a snapshot that is ONE packed group and nothing else (the resident index between merges) is searched a
+ *   "query_wg"           1 | 0 | 2   a snapshot that is ONE packed group and nothing else (the resident index between merges) is searched a
  *                        QUERY PER WORKGROUP -- dedup, probe, count and floor in one kernel, the hit records never leaving the CU
- *                        (csrc/fpx_qsearch.hpp; default 1) | by the pipeline below like every other snapshot
+ *                        (csrc/fpx_qsearch.hpp; default 1) | by the pipeline below like every other snapshot | as 1, and so is a
+ *                        packed group with superseded docs and/or columns outside the snapshot (a live index after updates, deletes
+ *                        or a merge without regroup), by the kernel's filtered form (fpx_stats.path_flags bit 8)
  *   "fast"               1 | 0   the device-sized path (one host round trip per batch; default 1)
  *   "binned"             1 | 0   groups drop their records into bins of a few queries, scored a bin per workgroup (default 1)
  *   "rec32"              1 | 0   4-byte records in the bins where the doc ids leave room (default 1)
@@ -207,9 +211,11 @@ int fpx_segment_download(const fpx_segment *seg, uint8_t *blocks, size_t blocks_
  * Segments snapshot order: file[] then memory[], oldest -> newest, commit_id strictly
  * ascending (src/Index.zig:36-41).  Builds the supersession tables.  Retains the segments.  A segment that is resident
  * on another context's device takes part with its docs map only (like fpx_segment_create_remote).
- * A snapshot of [one packed group without superseded docs] + [other file segments] -- a live index between merges -- is also laid out
- * in TWO PARTS that batches are searched through apart and merged (a doc lives in one segment; fpx_stats.path_flags bit 7): nothing
- * for the caller to do, a few hundred microseconds of snapshot creation. */
+ * A snapshot of [one packed group without superseded docs -- or, under "query_wg" 2, with] + [other file segments] -- a live index
+ * between merges -- is also laid out in TWO PARTS that batches are searched through apart and merged (a doc lives in one segment;
+ * fpx_stats.path_flags bit 7): nothing for the caller to do, a few hundred microseconds of snapshot creation.  The value of "query_wg"
+ * in force when the snapshot is created decides whether a group with superseded docs or masked columns may be part 0; such a part 0 is
+ * then searched a query per workgroup while the option is 2. */
 int  fpx_snapshot_create(fpx_ctx *ctx, fpx_segment *const *segs, uint32_t num_segs, fpx_snapshot **out);
 /* acquireReader / IndexReader.deinit (src/Index.zig:430-434, :157-163) */
 /* What fpx_snapshot_create made of the segments on this context: info[0..11] = file segments searched in their blocks by the
