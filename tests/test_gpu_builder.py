@@ -21,6 +21,9 @@ def env():
     (1, 20000, 40, 1, 4096),
     (7, 1, 3, 0, 512),            # a single partial quad
     (1, 300000, 16, 0, 512),      # many chunks: exercises the fixpoint across chunk boundaries
+    (0xFFFFFFFF - 2999, 3000, 33, 1, 512),     # doc ids ending at 0xFFFFFFFF
+    (0x80000000 - 1500, 3000, 40, 0, 64),      # doc ids straddling 2^31
+    (0xFFFFFFFF - 19999, 20000, 40, 1, 4096),
 ])
 def test_builder_bytes_match_reference_writer(env, first_doc, num_docs, H, dist, block_size):
     fpx, oracle, ctx = env

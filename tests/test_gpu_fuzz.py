@@ -17,7 +17,18 @@ def env():
     return fpx, oracle, Pair, fpx.Context(0)
 
 
-def random_world(fpx, Pair, ctx, rng, lean_sized):
+LAYOUTS = ("top", "straddle", "split")
+TOP = 0xFFFFFFFF
+
+
+def _first_id(layout, extent):
+    """where a world's ids start: `extent` = how far its file segments reach (new docs of memory segments go up to 1000 further, or
+    below the first id where that would pass 0xFFFFFFFF).  low: from 1; top: the files end at 0xFFFFFFFF; straddle: across 2^31;
+    split: from 1, every second file segment moved up by 0x90000000 (two clusters 2^31 or more apart)"""
+    return {"low": 1, "split": 1, "top": TOP - extent + 1, "straddle": (1 << 31) - extent // 2 - 1}[layout]
+
+
+def random_world(fpx, Pair, ctx, rng, lean_sized, layout="low"):
     p = Pair(ctx)
     n_file = int(rng.integers(1, 4)) if lean_sized else int(rng.integers(1, 6))
     H = 128 if lean_sized else int(rng.integers(3, 40))
@@ -26,12 +37,15 @@ def random_world(fpx, Pair, ctx, rng, lean_sized):
     stride = int(rng.choice([1, 1, 1, 7, 3001, 70001]))
     hot = rng.integers(0, 1 << hash_bits, 5, dtype=np.uint64)
     all_items = []
-    next_id = 1
+    first = _first_id(layout, n_file * ((per - 1) * stride + 1))
+    next_id = first
     commit = 0
     for s in range(n_file):
         commit += 1
         ids = next_id + np.arange(per, dtype=np.uint64) * stride
         next_id = int(ids[-1]) + 1
+        if layout == "split" and s % 2:
+            ids = ids + np.uint64(0x90000000)
         if s and rng.random() < 0.7:                      # re-insert / overwrite some docs of older segments
             older = np.unique(np.concatenate([x & np.uint64(0xFFFFFFFF) for x in all_items]))
             ids = np.unique(np.concatenate([ids, rng.choice(older, min(len(older), int(rng.integers(1, 60))), replace=False)]))
@@ -58,6 +72,8 @@ def random_world(fpx, Pair, ctx, rng, lean_sized):
                 changes.append(("delete", int(rng.choice(known))))
             else:
                 doc = int(rng.choice(known)) if rng.random() < 0.5 else next_id + int(rng.integers(0, 1000))
+                if doc > TOP:
+                    doc = first - 1 - (doc - next_id)
                 changes.append(("insert", doc, rng.integers(0, 1 << hash_bits, int(rng.integers(1, 30))).tolist() + [int(hot[0])]))
         p.add_memory_changes(changes, commit)
     return p.finish(), np.concatenate(all_items), hash_bits, hot
@@ -113,6 +129,21 @@ def test_fuzz_small_worlds(env, seed):
 
 
 @pytest.mark.parametrize("seed", range(16 * SCALE))
+def test_fuzz_high_doc_ids(env, seed):
+    """the small worlds with their ids at the top of the range (ending at 0xFFFFFFFF), straddling 2^31, or in two clusters 2^31 or
+    more apart (segments that re-insert docs of both span 2^31 and stay in their blocks; dead sets wider than 2^29)"""
+    fpx, oracle, Pair, ctx = env
+    rng = np.random.default_rng(50_000 + seed)
+    p, items, hash_bits, hot = random_world(fpx, Pair, ctx, rng, lean_sized=False, layout=LAYOUTS[seed % 3])
+    qs = random_queries(rng, items, hash_bits, hot, 48, int(rng.choice([5, 40, 300])))
+    p.check(qs, random_options(fpx, rng, len(qs)))
+    for q, o in list(zip(qs, random_options(fpx, rng, len(qs))))[:8]:
+        res = fpx.SearchResults(o)
+        p.reader.search(q, res)
+        assert res.getResults() == p.osnap.search(q, o.max_results, o.min_score, o.min_score_pct)
+
+
+@pytest.mark.parametrize("seed", range(16 * SCALE))
 def test_fuzz_lean_sized_worlds(env, seed, monkeypatch):
     """segments of > 2^20 items and batches of > 2^16 probes: the lean kernel + deferred pass carry these; every other
     world runs without the segments' presence bitmaps"""
@@ -128,12 +159,14 @@ def test_fuzz_lean_sized_worlds(env, seed, monkeypatch):
         assert st.probe_kernel_bytes > 0 and (DIRECT_FORCED or st.probe_aux_ms > 0)      # aux time is only taken next to the lean kernel
 
 
-@pytest.mark.parametrize("seed", range(24 * SCALE))
+# (seeds 1000 + k: the ids laid out as in test_fuzz_high_doc_ids)
+@pytest.mark.parametrize("seed", list(range(24 * SCALE)) + [1000, 1001, 1002])
 def test_fuzz_merge(env, seed):
     """random source ranges of random worlds through fpx_segment_merge against the oracle's SegmentMerger + writer"""
     fpx, oracle, Pair, ctx = env
     rng = np.random.default_rng(30_000 + seed)
-    p, items, hash_bits, hot = random_world(fpx, Pair, ctx, rng, lean_sized=False)
+    layout = LAYOUTS[seed % 3] if seed >= 1000 else "low"
+    p, items, hash_bits, hot = random_world(fpx, Pair, ctx, rng, lean_sized=False, layout=layout)
     nf, nm = len(p.orc_file), len(p.orc_mem)
     choices = []
     if nf:
@@ -155,7 +188,8 @@ def test_fuzz_merge(env, seed):
         assert np.array_equal(index, wi) and np.array_equal(blocks, wb)
 
 
-@pytest.mark.parametrize("seed", range(16 * SCALE))
+# (seeds 1000 + k: ids that end just below 0xFFFFFFFF, or that cross 2^31)
+@pytest.mark.parametrize("seed", list(range(16 * SCALE)) + [1000, 1001])
 def test_fuzz_sharded_modes(env, seed):
     """random worlds through BOTH multi-GPU decompositions emulated on one GPU: (a) whole segments per rank + docs-only
     stand-ins, partial tables, merge; (b) hash-range slices per rank, record exchange by doc & (world - 1), score,
@@ -167,20 +201,21 @@ def test_fuzz_sharded_modes(env, seed):
     n_file = int(rng.integers(2, 5))
     H, per, bits = int(rng.integers(8, 40)), int(rng.integers(300, 2000)), int(rng.choice([12, 20, 32]))
     hot = rng.integers(0, 1 << bits, 4, dtype=np.uint64)
-    files, next_id = [], 1
+    first = 1 if seed < 1000 else (TOP - n_file * per - 9, (1 << 31) - n_file * per // 2)[seed % 2]
+    files, next_id = [], first
     p = Pair(ctx)
     for s in range(n_file):
         ids = next_id + np.arange(per, dtype=np.uint64)
         next_id = int(ids[-1]) + 1
         if s:
-            ids = np.unique(np.concatenate([ids, rng.choice(np.arange(1, int(ids[0])), 40, replace=False).astype(np.uint64)]))
+            ids = np.unique(np.concatenate([ids, rng.choice(np.arange(first, int(ids[0])), 40, replace=False).astype(np.uint64)]))
         h = rng.integers(0, 1 << bits, (len(ids), H), dtype=np.uint64)
         m = rng.random(len(ids)) < 0.5
         h[m, 0] = hot[rng.integers(0, 4, int(m.sum()))]
         items = np.sort(((h << np.uint64(32)) | ids[:, None]).ravel())
         blocks, index = p.add_file(items, int(ids.min()), int(ids.max()), s + 1, ids.astype(np.uint32))
         files.append((blocks, index, int(ids.min()), int(ids.max()), s + 1, ids.astype(np.uint32)))
-    changes = [("delete", int(rng.integers(1, next_id))) for _ in range(3)] + [("insert", next_id + 5, [int(hot[0]), 1, 2])]
+    changes = [("delete", int(rng.integers(first, next_id))) for _ in range(3)] + [("insert", next_id + 5, [int(hot[0]), 1, 2])]
     p.add_memory_changes(changes, n_file + 1)
     p.finish()
     mem = oracle.memory_segment_from_changes(changes, n_file + 1)

@@ -20,12 +20,12 @@ def _rendezvous_file():
     return "file://" + path
 
 
-def _world_data(fpx, rng, S, per, H, seed):
+def _world_data(fpx, rng, S, per, H, seed, first=1):
     data = []
     for s in range(S):
-        lo = s * per + 1
+        lo = first + s * per
         ids = np.arange(lo, lo + per, dtype=np.uint64)
-        extra = np.sort(rng.choice(np.arange(1, lo), 200, replace=False)).astype(np.uint64) if s else np.zeros(0, np.uint64)
+        extra = np.sort(rng.choice(np.arange(first, lo, dtype=np.uint64), 200, replace=False)) if s else np.zeros(0, np.uint64)
         all_ids = np.concatenate([extra, ids])                       # later segments re-insert some older docs ...
         h = fpx.synth.synth_hashes(seed + s, all_ids, H, 1).astype(np.uint64)     # hot pool: runs spanning blocks, caps
         items = np.sort(((h << np.uint64(32)) | all_ids[:, None]).ravel())
@@ -37,7 +37,7 @@ def _world_data(fpx, rng, S, per, H, seed):
     return data
 
 
-def _sharded_world(world, monkeypatch):
+def _sharded_world(world, monkeypatch, first=1):
     """the unsharded index (GPU + oracle) and one reader per 'rank': the rank's window of every segment, cut on the device"""
     from fpx_testlib import fpx, oracle, Pair
     monkeypatch.setenv("FPX_DIRECT_MIN_ITEMS", "0")
@@ -45,7 +45,7 @@ def _sharded_world(world, monkeypatch):
     ctx = fpx.Context(0)
     seed, H, per, S = 31, 64, 5000, 3
     rng = np.random.default_rng(world)
-    data = _world_data(fpx, rng, S, per, H, seed)
+    data = _world_data(fpx, rng, S, per, H, seed, first)
     max_doc = max(hi for _, _, hi, _, _ in data)
     full = Pair(ctx)
     for s, (items, lo, hi, ids, alive) in enumerate(data):
@@ -159,10 +159,23 @@ def test_routed_keys_protocol_matches_unsharded_and_oracle(world, monkeypatch):
 
 @pytest.mark.parametrize("world", [2, 4, 8])
 def test_cells_of_hash_windows_match_unsharded_and_oracle(world, monkeypatch):
-    import torch
-    fpx, ctx, full, readers, (seed, H, per, S, max_doc) = _sharded_world(world, monkeypatch)
+    _check_cells(world, monkeypatch)
 
-    flat, off, _ = fpx.synth.make_queries(seed, 3, 150, per * S, H, query_len=300, dist=1)
+
+# The bins of the hash-window protocol hold 4-byte records (doc << 3 | query-in-bin) while the declared max doc is below
+# 0xFFFFFFFF >> 3 = 0x1FFFFFFF (csrc/fpx_search.hip, SHARD_BQ): a world whose last doc is 0x1FFFFFFE travels narrow, one whose last doc is
+# 0x1FFFFFFF -- or 0xFFFFFFFF -- wide
+@pytest.mark.parametrize("max_doc", [0x1FFFFFFE, 0x1FFFFFFF, 0xFFFFFFFF])
+def test_cells_at_the_record_width_threshold(max_doc, monkeypatch):
+    _check_cells(2, monkeypatch, first=max_doc - 3 * 5000 + 1)
+
+
+def _check_cells(world, monkeypatch, first=1):
+    import torch
+    fpx, ctx, full, readers, (seed, H, per, S, max_doc) = _sharded_world(world, monkeypatch, first)
+    narrow_expected = os.environ.get("FPX_REC32", "1") != "0" and max_doc < 0x1FFFFFFF
+
+    flat, off, _ = fpx.synth.make_queries(seed, 3, 150, per * S, H, query_len=300, dist=1, first_doc=first)
     flat = flat.copy()
     flat[5] = flat[4]                                                 # a duplicate hash inside a query
     bpr = fpx.shard_bins_per_rank(150, world)
@@ -195,7 +208,7 @@ def test_cells_of_hash_windows_match_unsharded_and_oracle(world, monkeypatch):
             c = counts.cpu().numpy().reshape(-1).astype(np.int64) & 0xFFFFFFFF
             narrow, c = (c >> 31) != 0, c & 0x7FFFFFFF                # bit 31 of a travelling count: the bin holds 4-byte records
             sv = send.cpu().numpy().reshape(world * bpr, cell_cap)
-            assert narrow.all() == (os.environ.get("FPX_REC32", "1") != "0")      # (doc ids of this world are far below 2^29)
+            assert narrow.all() == narrow_expected and narrow.any() == narrow_expected
             for b in range(world * bpr):
                 # (all ones: "no record" -- a workgroup's reservation in a bin is padded to whole 64-byte sectors, fpx_partition.hpp)
                 if narrow[b]:                                         # doc << 3 | query-in-bin, two to a cell

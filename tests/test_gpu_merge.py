@@ -42,6 +42,24 @@ def test_build_matches_reference_writer(env, n_docs, H, hash_bits, stride, block
     assert np.array_equal(seg.docs()[0], ids)
 
 
+@pytest.mark.parametrize("first_doc,n_docs,stride,block_size", [
+    (0xFFFFFFFF - 2999, 3000, 1, 512),            # ending at 0xFFFFFFFF
+    (0x80000000 - 70001 * 250, 500, 70001, 512),  # sparse across 2^31: 3- and 4-byte docid deltas
+    (0x80000000 - 1000, 2000, 1, 64),             # dense across 2^31
+])
+def test_build_at_high_doc_ids(env, first_doc, n_docs, stride, block_size):
+    fpx, oracle, ctx = env
+    rng = np.random.default_rng(first_doc & 0xFFFF)
+    items, ids = rand_items(rng, n_docs, first_doc, 40, 32, stride)
+    assert int(ids.max()) <= 0xFFFFFFFF
+    want_items = np.sort(items)
+    seg = fpx.FileSegment.build(ctx, items, block_size, int(ids.min()), int(ids.max()), 9, ids)
+    blocks, index = seg.download()
+    want_blocks, want_index = oracle.build_blocks(want_items, int(ids.min()), block_size)
+    assert np.array_equal(index, want_index) and np.array_equal(blocks, want_blocks)
+    assert np.array_equal(seg.docs()[0], ids)
+
+
 def test_build_rejects_bad_input(env):
     fpx, oracle, ctx = env
     items = np.array([(5 << 32) | 10, (4 << 32) | 11], np.uint64)
@@ -166,3 +184,38 @@ def test_merge_of_large_gpu_built_segments(env):
     merged, want, _ = check_merge(fpx, oracle, p, p.gpu_segs, p.orc_file, 512)
     assert merged.getSize() == len(a) + len(b) - (per // 10) * H          # the overwritten docs' old items are gone
     assert merged.num_blocks > 10000
+
+
+@pytest.mark.parametrize("block_size", [512, 64])
+def test_merge_spanning_2_31(env, block_size):
+    """a segment at the low end, one across 2^31 that re-inserts some of its docs, one ending at 0xFFFFFFFF and a memory segment that
+    deletes 0xFFFFFFFF and re-inserts a doc of each: merged bytes equal the oracle's merger + writer, the result spans 2^31 or more,
+    and the snapshot with the merged segment searches like the oracle"""
+    fpx, oracle, ctx = env
+    from fpx_testlib import Pair
+    rng = np.random.default_rng(231 + block_size)
+    p = Pair(ctx)
+    a_items, a_ids = rand_items(rng, 2000, 1, 24, 32)
+    p.add_file(np.sort(a_items), 1, 2000, 1, a_ids, block_size=block_size)
+    b_items, b_ids = rand_items(rng, 1500, 0x80000000 - 750, 24, 32)
+    again = np.array([5, 17, 1999], np.uint64)
+    h = rng.integers(0, 1 << 32, (len(again), 24), dtype=np.uint64)
+    b_items = np.sort(np.concatenate([b_items, ((h << np.uint64(32)) | again[:, None]).ravel()]))
+    b_ids = np.sort(np.concatenate([b_ids, again.astype(np.uint32)]))
+    p.add_file(b_items, int(b_ids.min()), int(b_ids.max()), 2, b_ids, block_size=block_size)
+    c_items, c_ids = rand_items(rng, 1000, 0xFFFFFFFF - 999, 24, 32)
+    p.add_file(np.sort(c_items), int(c_ids.min()), 0xFFFFFFFF, 3, c_ids, block_size=block_size)
+    p.add_memory_changes([("delete", 0xFFFFFFFF), ("insert", 0xFFFFFFFE, [1, 2, 3]), ("insert", 0x80000000, [4, 5]),
+                          ("insert", 3, [6, 7])], 4)
+    p.finish()
+    for lo, hi in ((0, 2), (1, 3), (0, 4)):
+        merged, want, (wb, wi) = check_merge(fpx, oracle, p, p.gpu_segs[lo:hi], (p.orc_file + p.orc_mem)[lo:hi], block_size)
+        assert want["max_doc_id"] - want["min_doc_id"] >= 1 << 31 or lo == 1
+    # the merged index of everything, searched
+    q = Pair(ctx)
+    q.add_file(want["items"], want["min_doc_id"], want["max_doc_id"], want["commit_id"], want["doc_ids"], want["doc_alive"], block_size=block_size)
+    q.gpu_segs = [merged]
+    q.finish()
+    items = want["items"]
+    queries = [(items[rng.integers(0, len(items), 30)] >> np.uint64(32)).astype(np.uint32).tolist() + [1, 2, 4, 6] for _ in range(32)]
+    q.check(queries, fpx.SearchOptions(max_results=50, min_score=2, min_score_pct=0))

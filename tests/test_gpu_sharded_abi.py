@@ -156,6 +156,15 @@ def test_an_index_without_segments_answers_with_no_results():
 
 @pytest.mark.parametrize("world", [2, 4, 8])
 def test_window_sharded_snapshot_routes_keys_behind_one_call(world, monkeypatch):
+    _window_sharded(world)
+
+
+def test_window_sharded_snapshot_across_2_31():
+    """the same with the index's doc ids from 2^31 - 10000 on: across 2^31, new docs of the memory segments near 2^31 + 900000"""
+    _window_sharded(2, first=(1 << 31) - 10000)
+
+
+def _window_sharded(world, first=1):
     """fpx_segment_create_file_windows + fpx_sharded_snapshot_create_windows + fpx_sharded_search_batch: the index sharded by hash range
     behind the one call (src/Index.zig:170-177 answers a search with one call) -- `world` contexts (distinct devices when the box has
     them), the batch's hashes split over them, keys routed to their window's rank, bins back to the rank the queries came from.  Same
@@ -170,10 +179,10 @@ def test_window_sharded_snapshot_routes_keys_behind_one_call(world, monkeypatch)
     full = Pair(ctxs[0])
     slices = [[] for _ in range(world)]
     for s in range(S):
-        lo = s * per + 1
+        lo = first + s * per
         ids = np.arange(lo, lo + per, dtype=np.uint64)
-        extra = np.sort(rng.choice(np.arange(1, lo), 200, replace=False)).astype(np.uint64) if s else np.zeros(0, np.uint64)
-        tomb = np.sort(rng.choice(np.setdiff1d(np.arange(1, lo), extra), 50, replace=False)).astype(np.uint64) if s else np.zeros(0, np.uint64)
+        extra = np.sort(rng.choice(np.arange(first, lo, dtype=np.uint64), 200, replace=False)) if s else np.zeros(0, np.uint64)
+        tomb = np.sort(rng.choice(np.setdiff1d(np.arange(first, lo, dtype=np.uint64), extra), 50, replace=False)) if s else np.zeros(0, np.uint64)
         live_ids = np.concatenate([extra, ids])
         h = fpx.synth.synth_hashes(seed + s, live_ids, H, 1).astype(np.uint64)       # hot pool: lists cut by the caps, runs across blocks
         items = np.sort(((h << np.uint64(32)) | live_ids[:, None]).ravel())
@@ -184,7 +193,7 @@ def test_window_sharded_snapshot_routes_keys_behind_one_call(world, monkeypatch)
         for k, sl in enumerate(fpx.file_segment_windows(ctxs, blocks, 512, index, mn, mx, s + 1, doc_ids, alive)):
             slices[k].append(sl)
     B = 200
-    flat, off, _ = fpx.synth.make_queries(seed, 3, B, S * per, H, query_len=160, dist=1)
+    flat, off, _ = fpx.synth.make_queries(seed, 3, B, S * per, H, query_len=160, dist=1, first_doc=first)
     flat = flat.copy()
     flat[9] = flat[8]                                                 # a duplicate hash inside a query
     queries = [flat[int(off[i]):int(off[i + 1])] for i in range(B)]
@@ -192,8 +201,9 @@ def test_window_sharded_snapshot_routes_keys_behind_one_call(world, monkeypatch)
     # after the file segments, :173-175) -- new docs that match queries, an old doc re-inserted with other hashes (its file postings are
     # superseded), a delete.  Every rank holds a copy of each memory segment and looks up the keys of its window in it.
     q0, q1 = [int(h) for h in queries[0][:60]], [int(h) for h in queries[57][:90]]
-    for changes in ([("insert", 900001, q0), ("insert", 7, q1[:40]), ("delete", 11)],
-                    [("insert", 900002, q1), ("insert", 900001, q0[:30] + q1[:20]), ("delete", per + 3)]):
+    new1, new2 = first + 900000, first + 900001
+    for changes in ([("insert", new1, q0), ("insert", first + 6, q1[:40]), ("delete", first + 10)],
+                    [("insert", new2, q1), ("insert", new1, q0[:30] + q1[:20]), ("delete", first + per + 2)]):
         commit = len(full.gpu_segs) + 1
         full.add_memory_changes(changes, commit)
         m = full.orc_mem[-1]
@@ -221,7 +231,7 @@ def test_window_sharded_snapshot_routes_keys_behind_one_call(world, monkeypatch)
     mixed = [fpx.http_options()] * 15 + [fpx.SearchOptions(500, 2, 10)]
     got, _ = sh.search_batch(queries[:16], mixed)
     assert got == [full.osnap.search(q, o.max_results, o.min_score, o.min_score_pct) for q, o in zip(queries[:16], mixed)]
-    assert 900001 in [d for d, _ in got[0]], got[0][:5]
+    assert new1 in [d for d, _ in got[0]], got[0][:5]
     # many host threads on the one snapshot
     want = [full.osnap.search(q) for q in queries[:64]]
     errs = []

@@ -86,7 +86,8 @@ def block_starts_of(blocks, block_size, nblocks):
     return np.concatenate([[0], np.cumsum(n)[:-1]]).astype(np.int64).tolist() if nblocks else []
 
 
-def make_world(block_size, seed):
+def make_world(block_size, seed, base=1):
+    """three file segments of 2500+ docs from doc `base` on (the ids base .. base + 7499) and a memory segment over them"""
     rng = np.random.default_rng(seed)
     raws, ofile, omem = [], [], []
     H = 24
@@ -94,10 +95,10 @@ def make_world(block_size, seed):
     commit = 0
     for s in range(3):
         commit += 1
-        lo = s * 2500 + 1
+        lo = base + s * 2500
         ids = np.arange(lo, lo + 2500 + (3 if s == 1 else 0), dtype=np.uint64)   # s == 1: item count not a multiple of 4
         if s:
-            ids = np.sort(np.concatenate([ids, rng.choice(np.arange(1, lo), 120, replace=False).astype(np.uint64)]))
+            ids = np.sort(np.concatenate([ids, rng.choice(np.arange(base, lo, dtype=np.uint64), 120, replace=False)]))
         h = rng.integers(0, 1 << 32, (len(ids), H), dtype=np.uint64)
         h[:, 0] = np.where(rng.random(len(ids)) < 0.6, hot[rng.integers(0, 6, len(ids))], h[:, 0])
         h[:, 1] = h[:, 0]                                            # duplicate postings inside a doc
@@ -110,7 +111,7 @@ def make_world(block_size, seed):
         raws.append(RawSegment(items, block_starts_of(blocks, block_size, len(index)), commit, ids, alive, int(ids.min()), int(ids.max())))
     # a memory segment with tombstones for popular docs and an overwrite
     commit += 1
-    changes = [("delete", 7), ("delete", 2600), ("insert", 11, [int(hot[0]), int(hot[1]), 5]), ("delete", 5100)]
+    changes = [("delete", base + 6), ("delete", base + 2599), ("insert", base + 10, [int(hot[0]), int(hot[1]), 5]), ("delete", base + 5099)]
     m = oracle.memory_segment_from_changes(changes, commit)
     omem.append(m)
     mids, malive = m.docs()
@@ -118,9 +119,7 @@ def make_world(block_size, seed):
     return raws, oracle.Snapshot(ofile, omem), hot, rng
 
 
-@pytest.mark.parametrize("block_size", [64, 512, 4096])
-def test_oracle_equals_brute_force_on_unpinned_behaviour(block_size):
-    raws, snap, hot, rng = make_world(block_size, 1000 + block_size)
+def _check_against_brute_force(raws, snap, hot, rng):
     all_h = np.concatenate([r.h for r in raws[:3]])
     queries = []
     for i in range(40):
@@ -137,6 +136,20 @@ def test_oracle_equals_brute_force_on_unpinned_behaviour(block_size):
             assert (st.scanned_blocks, st.scanned_docs) == (wb, wd)
         hit_caps = hit_caps or wd > MAX_DOCS_PER_HASH
     assert hit_caps                                                  # the truncation rules were really exercised
+
+
+@pytest.mark.parametrize("block_size", [64, 512, 4096])
+def test_oracle_equals_brute_force_on_unpinned_behaviour(block_size):
+    _check_against_brute_force(*make_world(block_size, 1000 + block_size))
+
+
+# doc ids across 2^31 and up to 0xFFFFFFFF: the GPU tests of tests/test_gpu_doc_ids.py trust the oracle there
+@pytest.mark.parametrize("block_size,base", [(512, 0x80000000 - 3750), (4096, 0xFFFFFFFF - 7499)], ids=["straddle", "top"])
+def test_oracle_equals_brute_force_at_high_doc_ids(block_size, base):
+    raws, snap, hot, rng = make_world(block_size, 1000 + block_size, base)
+    lo, hi = min(r.min_doc for r in raws), max(r.max_doc for r in raws)
+    assert (lo < 0x80000000 <= hi) if base < 0x80000000 else hi == 0xFFFFFFFF
+    _check_against_brute_force(raws, snap, hot, rng)
 
 
 def test_brute_force_reproduces_reference_vectors():

@@ -66,6 +66,29 @@ def test_round_trip_and_corruption(tmp_path):
         fpx.segfile.read_segment_file(bad)
 
 
+def test_round_trip_of_doc_ids_across_2_31_and_at_the_top(tmp_path):
+    """docs 0x7FFFFF00 .. 0x800000FF and 0xFFFFFF00 .. 0xFFFFFFFF (0x80000000 and 0xFFFFFFFF among them), a tombstone at 0xFFFFFFFE:
+    the doc map (msgpack uint32 keys), the blocks built from min_doc_id 0x7FFFFF00 and the doc id range come back as written"""
+    ids = np.concatenate([np.arange(0x7FFFFF00, 0x80000100, dtype=np.uint64), np.arange(0xFFFFFF00, 0x100000000, dtype=np.uint64)])
+    rng = np.random.default_rng(5)
+    h = rng.integers(0, 1 << 32, (len(ids), 12), dtype=np.uint64)
+    items = np.unique(((h << np.uint64(32)) | ids[:, None]).ravel())
+    blocks, index = oracle.build_blocks(items, int(ids[0]), 512)
+    docs = {int(i): True for i in ids}
+    docs[0xFFFFFFFE] = False
+    path = os.path.join(str(tmp_path), fpx.segfile.segment_file_name(9, 0))
+    fpx.segfile.write_segment_file(path, (9, 0, None), docs, blocks, index, 512)
+    s = fpx.segfile.read_segment_file(path)
+    assert s["num_items"] == len(items)
+    assert np.array_equal(s["blocks"], blocks) and np.array_equal(s["block_index"], index)
+    assert dict(zip(s["doc_ids"].tolist(), (bool(a) for a in s["doc_alive"]))) == docs
+    assert 0x80000000 in s["doc_ids"].tolist() and s["doc_ids"].dtype == np.uint32
+    assert (s["min_doc_id"], s["max_doc_id"]) == (0x7FFFFF00, 0xFFFFFFFF)
+    dec = [oracle.block_decode_items(blocks[b * 512:(b + 1) * 512], int(ids[0])) for b in range(len(index))]
+    got = np.concatenate([(h.astype(np.uint64) << np.uint64(32)) | d.astype(np.uint64) for h, d in dec])
+    assert np.array_equal(np.sort(got), items)
+
+
 def test_manifest_round_trip(tmp_path):
     d = str(tmp_path)
     assert fpx.segfile.read_manifest(d) == []
