@@ -90,6 +90,19 @@ struct QSearchArgs {
     uint32_t stagger;                                          // delays of 3.4 us between the start of a CU's workgroups (0: none)
 };
 
+// The kernel's arguments as its two by-value parameters lay them out in the kernel-argument segment.  Most of them are needed once per
+// query, at its head or tail; held in scalar registers for the whole kernel they crowded out the rounds' own scalars (90 spilled into lanes
+// of eight vector registers, which in turn spilled to scratch).  Those are read where they are used: qs_cold_args() is the segment's
+// address behind a barrier to hoisting, so that a load through it stays at its use and costs no register elsewhere.
+struct QSKernargs { QSearchArgs a; GroupArgs ga; };
+typedef const __attribute__((address_space(4))) QSKernargs* qs_kargs_t;
+__device__ __forceinline__ qs_kargs_t qs_cold_args()
+{
+    qs_kargs_t p = (qs_kargs_t)__builtin_amdgcn_kernarg_segment_ptr();
+    asm volatile("" : "+s"(p));
+    return p;
+}
+
 #define FPX_QS_OCC __attribute__((amdgpu_waves_per_eu(FPX_QS_WAVES)))
 typedef uint32_t u32x3_t __attribute__((ext_vector_type(3)));
 __device__ __forceinline__ uint3 gload_u3(const uint32_t* p)            // the first three words of a line (16-byte aligned)
@@ -127,7 +140,7 @@ __device__ __forceinline__ uint32_t qs_word_cols(uint32_t pm, uint32_t dm, uint3
 // (FPX_QS_PROF: an experiment build -- wave 0 of every workgroup adds the clocks it spent between the kernel's phases to the batch's
 // counters [16 ..], which the host prints; tools/build_variant.sh qs_prof -DFPX_QS_PROF=1)
 #ifdef FPX_QS_PROF
-#define QS_MARK(i) do { if (tid == 0) { const unsigned long long t_ = clock64(); atomicAdd(&a.counters[CTR_HIST + (i)], t_ - t_prev); t_prev = t_; } } while (0)
+#define QS_MARK(i) do { if (tid == 0) { const unsigned long long t_ = clock64(); atomicAdd(&qs_cold_args()->a.counters[CTR_HIST + (i)], t_ - t_prev); t_prev = t_; } } while (0)
 #else
 #define QS_MARK(i) do { } while (0)
 #endif
@@ -167,9 +180,16 @@ __global__ __launch_bounds__(QS_WG) FPX_QS_OCC void k_search_query(QSearchArgs a
     uint64_t q_lo = a.offsets[q];
     uint32_t n = (uint32_t)(a.offsets[q + 1] - q_lo);
     const uint32_t* qh = a.hashes_base + q_lo;
-    if (tid < FUSE_MAX) { s_first[tid] = g->first_hash[tid]; s_last[tid] = g->last_hash[tid]; }
-    if (tid < GROUP_CHUNKS) s_ext[tid] = tid < g->nchunks ? g->ext_tab[tid] : nullptr;
-    if (FILT && tid < FUSE_MAX) s_dseg[tid] = g->has_dead[tid] != 0u ? g->seg_index[tid] : 0xFFFFFFFFu;
+    {
+        const qs_kargs_t ka = qs_cold_args();
+        if (tid < FUSE_MAX) { s_first[tid] = ka->ga.g.first_hash[tid]; s_last[tid] = ka->ga.g.last_hash[tid]; }
+        if (tid < GROUP_CHUNKS) s_ext[tid] = tid < ka->ga.g.nchunks ? ka->ga.g.ext_tab[tid] : nullptr;
+        if (FILT && tid < FUSE_MAX) s_dseg[tid] = ka->ga.g.has_dead[tid] != 0u ? ka->ga.g.seg_index[tid] : 0xFFFFFFFFu;
+    }
+    // (records are docs - gmin inside the workgroup -- what the line's words hold --; gmin is added once per candidate at hand-over.  Only the
+    // supersession test (FILT) and the memory segments' absolute docs (MEM) need it before that)
+    const uint32_t gmin = (FILT || MEM) ? g->gmin : 0u;
+    (void)gmin;
     // ---- the first QS_CH rounds' hashes and the heads of their lines (position bits, double flags) set out at once: a round is a chain
     //      of latencies -- hash, line head (HBM), words, ... -- and a CU holds sixteen waves to overlap them; what does not depend on the
     //      round before it is asked for up front.  (A duplicate's line is fetched for nothing: dedup runs while the heads travel.)
@@ -200,8 +220,8 @@ __global__ __launch_bounds__(QS_WG) FPX_QS_OCC void k_search_query(QSearchArgs a
   // they end together and the next kernel starts in lockstep again (0.412 -> 0.43 ms per batch, and jittery).  So the host asks for both -- the
   // counter and the delays -- only for a batch that finds the device to itself (run_batch: Ctx::qs_running).
   // Only where a workgroup has four or more queries ahead of it: a small batch is one query's latency.
-  if (a.stagger != 0u && a.q_end - a.q_begin >= 4u * gridDim.x)
-      for (uint32_t i = 0; i < ((blockIdx.x >> 8) & 3u) * a.stagger; ++i) __builtin_amdgcn_s_sleep(127);
+  if (const uint32_t stagger = qs_cold_args()->a.stagger; stagger != 0u && a.q_end - a.q_begin >= 4u * gridDim.x)
+      for (uint32_t i = 0; i < ((blockIdx.x >> 8) & 3u) * stagger; ++i) __builtin_amdgcn_s_sleep(127);
   for (;;) {
     const uint32_t rounds = (n + QS_WG - 1u) / QS_WG, nchunks = (rounds + QS_CH - 1u) / QS_CH;
     // the query's hash set: 2^sbits >= 2 n slots
@@ -212,7 +232,8 @@ __global__ __launch_bounds__(QS_WG) FPX_QS_OCC void k_search_query(QSearchArgs a
     if (tid == 0) {
         s_count = 0u; s_ntask = 0u; s_over_recs = 0u; s_seen_ones = 0u; s_ccnt = 0u; s_cshared = 0u;
         wg_blocks = 0; wg_docs = 0; wg_probes = 0; wg_reads = 0;
-        s_cancel = cancel_requested(a.cancel, a.counters) ? 1u : 0u;        // cancel point (src/FileSegment.zig:144), once per query
+        const qs_kargs_t ka = qs_cold_args();
+        s_cancel = cancel_requested(ka->a.cancel, ka->a.counters) ? 1u : 0u;  // cancel point (src/FileSegment.zig:144), once per query
     }
     __syncthreads();
     if (s_cancel) return;
@@ -270,8 +291,10 @@ __global__ __launch_bounds__(QS_WG) FPX_QS_OCC void k_search_query(QSearchArgs a
         return di != 0xFFFFFFFFu && is_dead_seg(ga.segs[di], doc);
     };
     // ---- records.  `n` docs of the lane (mask km over d[]) join the query's array: one reservation per wave -- a scan on the DPP
-    //      crossbar: the whole wave is here (fpx_pgroup.hpp x5) --, doc j at pos + (docs of the lane before it); a slot without a doc
-    //      writes the sink word behind the array (no branch per slot).  The filter is counted later, over the array (every lane busy).
+    //      crossbar: the whole wave is here (fpx_pgroup.hpp x5) --, doc j at pos + (docs of the lane before it).  No branch and no select
+    //      per slot: the slots are stored from the LAST down, a slot without a doc to where the nearest doc BELOW it goes -- a place of the
+    //      lane's own that the doc itself, stored later, overwrites (a lane's stores to LDS keep their order); one with no doc below it, and
+    //      every slot of a lane without docs, to the sink word behind the array.  The filter is counted later, over the array (every lane busy).
     auto reserve_in = [&](uint32_t* counter, uint32_t cnt) -> uint32_t {
         const uint32_t incl = scan16(cnt);
         const uint32_t r0 = (uint32_t)__builtin_amdgcn_readlane((int)incl, 15), r1 = (uint32_t)__builtin_amdgcn_readlane((int)incl, 31),
@@ -285,17 +308,41 @@ __global__ __launch_bounds__(QS_WG) FPX_QS_OCC void k_search_query(QSearchArgs a
         const uint32_t row = lane >> 4;
         return wbase + (row >= 1u ? r0 : 0u) + (row >= 2u ? r1 : 0u) + (row >= 3u ? r2 : 0u) + (incl - cnt);
     };
-    auto reserve = [&](uint32_t cnt) -> uint32_t { return reserve_in(&s_count, cnt); };
-    auto emit = [&](uint32_t km, const auto& d) {
-        constexpr uint32_t N = sizeof(d) / sizeof(uint32_t);
-        const uint32_t cnt = (uint32_t)__popc(km);
-        const uint32_t pos = reserve(cnt);
-        if (cnt != 0u && pos + cnt > QS_REC_CAP) s_over_recs = 1u;               // (more records than the array takes: the batch goes the long way)
-#pragma unroll
-        for (uint32_t j = 0; j < N; ++j) {
-            const uint32_t at = pos + (uint32_t)__popc(km & ((1u << j) - 1u));
-            recs[(((km >> j) & 1u) != 0u && at < QS_REC_CAP) ? at : QS_REC_CAP] = d[j];
+    // (a round reserves its records and its tasks with ONE scan: the two counts side by side in a word -- a wave has at most 64 x 12
+    // records and far fewer than 2^16 tasks --, an atomic per counter)
+    auto reserve_both = [&](uint32_t cnt, uint32_t nt, uint32_t& tat) -> uint32_t {
+        const uint32_t both = cnt | (nt << 16);
+        const uint32_t incl = scan16(both);
+        const uint32_t r0 = (uint32_t)__builtin_amdgcn_readlane((int)incl, 15), r1 = (uint32_t)__builtin_amdgcn_readlane((int)incl, 31),
+                       r2 = (uint32_t)__builtin_amdgcn_readlane((int)incl, 47), r3 = (uint32_t)__builtin_amdgcn_readlane((int)incl, 63);
+        const uint32_t total = r0 + r1 + r2 + r3;
+        uint32_t rbase = 0, tbase = 0;
+        if ((total & 0xFFFFu) != 0u) {                                           // (wave-uniform)
+            if (lane == 0u) rbase = atomicAdd(&s_count, total & 0xFFFFu);
+            rbase = (uint32_t)__builtin_amdgcn_readfirstlane((int)rbase);
         }
+        if ((total >> 16) != 0u) {
+            if (lane == 0u) tbase = atomicAdd(&s_ntask, total >> 16);
+            tbase = (uint32_t)__builtin_amdgcn_readfirstlane((int)tbase);
+        }
+        const uint32_t row = lane >> 4;
+        const uint32_t before = (row >= 1u ? r0 : 0u) + (row >= 2u ? r1 : 0u) + (row >= 3u ? r2 : 0u) + (incl - both);
+        tat = tbase + (before >> 16);
+        return rbase + (before & 0xFFFFu);
+    };
+    auto emit_at = [&](uint32_t km, const auto& d, uint32_t cnt, uint32_t pos) {            // (km: bits 0 .. N-1 only; cnt of them, from pos)
+        constexpr uint32_t N = sizeof(d) / sizeof(uint32_t);
+        if (cnt != 0u && pos + cnt > QS_REC_CAP) { s_over_recs = 1u; km = 0u; cnt = 0u; }      // (more records than the array takes: the batch goes the long way)
+        const uint32_t first = cnt != 0u ? pos : QS_REC_CAP, sink = QS_REC_CAP - first;
+#pragma unroll
+        for (uint32_t j = N; j-- != 0u;) {
+            const uint32_t last = (uint32_t)__popc(km & ((2u << j) - 1u)) - 1u;      // the last doc up to slot j among the lane's (none: 0xFFFFFFFF)
+            recs[first + min(last, sink)] = d[j];
+        }
+    };
+    auto emit = [&](uint32_t km, const auto& d) {
+        const uint32_t cnt = (uint32_t)__popc(km);
+        emit_at(km, d, cnt, reserve_in(&s_count, cnt));
     };
     // (one record of some lanes of the wave: the wave's turns, long lists)
     auto emit1 = [&](bool kp, uint32_t doc) {
@@ -353,25 +400,28 @@ __global__ __launch_bounds__(QS_WG) FPX_QS_OCC void k_search_query(QSearchArgs a
         const uint32_t start = hx & 127u, mine = (hx >> 7) & 15u, nwords = (hx >> 11) & 63u, inl = (hx >> 17) & 31u;
         // (outside [first_hash, last_hash] the reference visits no block, src/FileSegment.zig:164,153)
         uint32_t inr = active;
-        if (h < g->lo_all || h > g->hi_all) {
-            inr = 0u;
+        if (h < g->lo_all || h > g->hi_all) {          // (rare: the columns' bounds stay in LDS -- read through an index the compiler cannot
+            inr = 0u;                                  // see through, or it keeps all 2 NS of them in registers across the rounds)
+            uint32_t z = 0u;
+            asm volatile("" : "+v"(z));
 #pragma unroll
-            for (uint32_t s = 0; s < NS; ++s) inr |= (h >= s_first[s] && h <= s_last[s]) ? (1u << s) : 0u;
+            for (uint32_t s = 0; s < NS; ++s) inr |= (h >= s_first[z + s] && h <= s_last[z + s]) ? (1u << s) : 0u;
         }
         if (!valid) inr = 0u;
         my_blocks += (uint32_t)__popc(inr & active & ~pm);         // absent: the reference visits one block, finds nothing and stops
         // second words of doubles: the t-th double, at position i, has its second word at i + t + 1
         uint32_t second = 0;
         for (uint32_t d = dm, t = 0; d != 0u; d &= d - 1u, ++t) second |= 1u << ((uint32_t)__builtin_ctz(d) + t + 1u);
-        uint32_t keep = 0, lmask = 0;
+        uint32_t negm = 0, gapm = 0;
 #pragma unroll
         for (uint32_t j = 0; j < QS_WORDS; ++j) {
             const uint32_t word = gw[j];
-            const bool v = j < mine, neg = (int32_t)word < 0;
-            keep |= (v && !neg) ? (1u << j) : 0u;                               // a doc (a gap position and a list reference have bit 31)
-            lmask |= (v && neg && word != 0xFFFFFFFFu) ? (1u << j) : 0u;        // a list reference
-            gw[j] = neg ? word : g->gmin + word;
+            negm |= (word >> 31) << j;                                          // a gap position and a list reference have bit 31
+            gapm |= (word == 0xFFFFFFFFu ? 1u : 0u) << j;
         }
+        const uint32_t vm = (1u << mine) - 1u;
+        uint32_t keep = vm & ~negm;                                             // the docs among the lane's words
+        uint32_t lmask = vm & negm & ~gapm;                                     // its list references
         // (FILT) the walked words by their column (k_probe_pgroup's walk, a column's one or two words at a time): words of a column outside
         // the snapshot are nothing; dmask: the words whose column has superseded docs.  (A word's own column, where it is needed -- a
         // doc of such a column, a list reference --, is walked to again: no register holds the twelve)
@@ -396,10 +446,9 @@ __global__ __launch_bounds__(QS_WG) FPX_QS_OCC void k_search_query(QSearchArgs a
                 uint32_t doc = 0;
 #pragma unroll
                 for (uint32_t j = 0; j < QS_WORDS; ++j) doc = j == j0 ? gw[j] : doc;
-                if (dead_in(qs_word_cols(pm, dm, j0, 1u), doc)) keep &= ~(1u << j0);
+                if (dead_in(qs_word_cols(pm, dm, j0, 1u), gmin + doc)) keep &= ~(1u << j0);
             }
         }
-        emit(keep, gw);
         // ---- what the round does not wait for joins the query's task queue -- the hash's lists (their heads are other lines: HBM), its
         //      words beyond the lane's own and those that overflowed the line into `ext` --; the workgroup takes the tasks up together
         //      once its rounds are done
@@ -408,7 +457,9 @@ __global__ __launch_bounds__(QS_WG) FPX_QS_OCC void k_search_query(QSearchArgs a
         const uint32_t in_line = (nwords != mine && start + mine < inl) ? min(nwords - mine, inl - (start + mine)) : 0u;
         const uint32_t in_ext = nwords - mine - in_line;
         const uint32_t nt = (uint32_t)__popc(lmask) + (in_line + QS_TASK_WORDS - 1u) / QS_TASK_WORDS + (in_ext + QS_TASK_WORDS - 1u) / QS_TASK_WORDS;
-        uint32_t tat = reserve_in(&s_ntask, nt);
+        uint32_t tat;
+        const uint32_t nrec = (uint32_t)__popc(keep);
+        emit_at(keep, gw, nrec, reserve_both(nrec, nt, tat));
         if (nt != 0u) {
             if (tat + nt > TCAP) { s_over_recs = 1u; tat = TCAP; }                // (a full queue: the batch goes the long way)
             auto put_task = [&](unsigned long long e) { if (tat < TCAP) tasks[tat] = e; ++tat; };
@@ -481,7 +532,7 @@ __global__ __launch_bounds__(QS_WG) FPX_QS_OCC void k_search_query(QSearchArgs a
                     if ((uint32_t)(it >> 32) > mh[u]) break;
                     if ((uint32_t)(it >> 32) == mh[u]) {
                         const uint32_t at = atomicAdd(&s_count, 1u);
-                        if (at < QS_REC_CAP) recs[at] = (uint32_t)it; else s_over_recs = 1u;
+                        if (at < QS_REC_CAP) recs[at] = (uint32_t)it - gmin; else s_over_recs = 1u;      // (a memory segment's doc may lie below gmin: modulo 2^32)
                     }
                 }
         }
@@ -491,7 +542,7 @@ __global__ __launch_bounds__(QS_WG) FPX_QS_OCC void k_search_query(QSearchArgs a
     // ---- the NEXT query's offsets and hashes set out now (the chunk registers are free): they travel under this query's tasks and counting
     // (... and the query after THAT is asked of the launch's counter: the answer has the tasks and the counting to arrive in)
     uint32_t r2 = 0u;
-    if (tid == 0u && a.next_q != nullptr) r2 = atomicAdd(a.next_q, 1u);
+    if (tid == 0u) { unsigned int* const next_q = qs_cold_args()->a.next_q; if (next_q != nullptr) r2 = atomicAdd(next_q, 1u); }
     const uint32_t qn = qn1;
     const bool has_next = qn < a.q_end;                      // (uniform)
     uint64_t nq_lo = 0; uint32_t nn = 0;
@@ -544,17 +595,18 @@ __global__ __launch_bounds__(QS_WG) FPX_QS_OCC void k_search_query(QSearchArgs a
                     if (long_list) my_reads += ((eff - xin + 31u) >> 5) * 2u;
                 } else if (has) {
                     const uint32_t second = (uint32_t)(e >> 49) & 0xFFu;
+                    uint32_t vm = (1u << cnt) - 1u, negm = 0, gapm = 0;
 #pragma unroll
                     for (uint32_t j = 0; j < QS_TASK_WORDS; ++j) {
-                        const bool v = j < cnt && (!FILT || ((active >> ((tc >> (4u * j)) & 15u)) & 1u) != 0u), neg = (int32_t)d[j] < 0;
-                        km |= (v && !neg) ? (1u << j) : 0u;
-                        lm |= (v && neg && d[j] != 0xFFFFFFFFu) ? (1u << j) : 0u;
+                        if constexpr (FILT) vm &= ~((((active >> ((tc >> (4u * j)) & 15u)) & 1u) ^ 1u) << j);
+                        negm |= (d[j] >> 31) << j;
+                        gapm |= (d[j] == 0xFFFFFFFFu ? 1u : 0u) << j;
                     }
+                    km = vm & ~negm;
+                    lm = vm & negm & ~gapm;
                     my_docs += (uint32_t)__popc(km); my_blocks += (uint32_t)__popc(km & ~second);
                     if constexpr (SCAN_HIST && (FPX_SH_BITS & 2)) my_probes += (uint32_t)__popc(km & second) << 16;
                 }
-#pragma unroll
-                for (uint32_t j = 0; j < QS_TASK_WORDS; ++j) d[j] = ((int32_t)d[j] < 0 && !is_list) ? d[j] : g->gmin + d[j];
                 if constexpr (FILT) {                   // (counted above: before supersession)
                     for (uint32_t m = km; m != 0u; m &= m - 1u) {
                         const uint32_t j0 = (uint32_t)__builtin_ctz(m);
@@ -563,7 +615,7 @@ __global__ __launch_bounds__(QS_WG) FPX_QS_OCC void k_search_query(QSearchArgs a
                         uint32_t doc = 0;
 #pragma unroll
                         for (uint32_t j = 0; j < QS_TASK_WORDS; ++j) doc = j == j0 ? d[j] : doc;
-                        if (dead_in(s, doc)) km &= ~(1u << j0);
+                        if (dead_in(s, gmin + doc)) km &= ~(1u << j0);
                     }
                 }
                 emit(km, d);
@@ -586,8 +638,8 @@ __global__ __launch_bounds__(QS_WG) FPX_QS_OCC void k_search_query(QSearchArgs a
                     const uint32_t col_s = FILT ? (uint32_t)__shfl(lcol, src) : 0u;
                     for (uint32_t o2 = from; o2 < eff_s; o2 += 64u) {
                         bool kp = o2 + lane < eff_s;
-                        const uint32_t dv = g->gmin + (kp ? gload_u32(list + 1u + T_s + o2 + lane) : 0u);
-                        if constexpr (FILT) { if (kp) kp = !dead_in(col_s, dv); }
+                        const uint32_t dv = kp ? gload_u32(list + 1u + T_s + o2 + lane) : 0u;
+                        if constexpr (FILT) { if (kp) kp = !dead_in(col_s, gmin + dv); }
                         emit1(kp, dv);
                     }
                 }
@@ -631,25 +683,28 @@ __global__ __launch_bounds__(QS_WG) FPX_QS_OCC void k_search_query(QSearchArgs a
             if (i + u < nrec) atomicAdd(&filter[c >> 1], 1u << (16u * (c & 1u)));
         }
     }
+    const qs_kargs_t kt = qs_cold_args();               // (the tail's arguments: read here, once per query)
     if (tid == 0) {
-        unsigned long long* st = a.stat_sets + (size_t)(q % LEAN_STAT_SETS) * 8u;
+        unsigned long long* st = kt->a.stat_sets + (size_t)(q % LEAN_STAT_SETS) * 8u;
         if (wg_reads) atomicAdd(&st[4], wg_reads);
         if (wg_blocks) atomicAdd(&st[1], wg_blocks);
-        if (wg_blocks && g->block_size != 512u) atomicAdd(&st[5], wg_blocks * (unsigned long long)g->block_size - wg_blocks * 512ull);
+        const uint32_t block_size = kt->ga.g.block_size;
+        if (wg_blocks && block_size != 512u) atomicAdd(&st[5], wg_blocks * (unsigned long long)block_size - wg_blocks * 512ull);
         if (wg_docs) atomicAdd(&st[2], wg_docs);
         if (wg_probes) atomicAdd(&st[3], wg_probes);
         if (s_count) atomicAdd(&st[7], (unsigned long long)s_count);                  // the query's hit records
-        if (QS && a.qstats) a.qstats[q] = wg_blocks | (wg_docs << 32);
-        if (s_over_recs || s_count > QS_REC_CAP) atomicMax(&a.counters[CTR_BINFAIL], 1ull);
+        if constexpr (QS) { unsigned long long* const qstats = kt->a.qstats; if (qstats) qstats[q] = wg_blocks | (wg_docs << 32); }
+        if (s_over_recs || s_count > QS_REC_CAP) atomicMax(&kt->a.counters[CTR_BINFAIL], 1ull);
     }
     if (tid < HIST_SLOTS - 1u) {                             // (slot 15: hist_observe's sink)
         const unsigned long long v = tid == HIST_COUNT ? wg_probes : tid == HIST_DOCS ? wg_docs : tid == HIST_BLOCKS ? wg_blocks : (unsigned long long)wg_h[tid];
-        if (v != 0ull) atomicAdd(&a.stat_sets[(size_t)LEAN_STAT_SETS * 8u + (size_t)(q % LEAN_STAT_SETS) * HIST_SLOTS + tid], v);
+        if (v != 0ull) atomicAdd(&kt->a.stat_sets[(size_t)LEAN_STAT_SETS * 8u + (size_t)(q % LEAN_STAT_SETS) * HIST_SLOTS + tid], v);
     }
     // ---- ... then the floor of finish (src/common.zig:131-145): a doc can only reach the floor if its cell did; those records are
     //      counted exactly, in `passes` loads over classes of them when they are more than the table takes
-    const uint32_t floor_q = a.opts[q * 4u + 1u];
-    const uint64_t smax = a.sb >= 32u ? 0xFFFFFFFFull : ((1ull << a.sb) - 1ull);
+    const uint32_t floor_q = kt->a.opts[q * 4u + 1u];
+    const uint32_t sb = kt->a.sb;
+    const uint64_t smax = sb >= 32u ? 0xFFFFFFFFull : ((1ull << sb) - 1ull);
     if (s_over_recs == 0u && nrec != 0u && nrec >= floor_q) {
         uint32_t passes = 1u;
         for (uint32_t pass = 0; pass < passes; ++pass) {
@@ -694,22 +749,24 @@ __global__ __launch_bounds__(QS_WG) FPX_QS_OCC void k_search_query(QSearchArgs a
                 passes = np; pass = 0xFFFFFFFFu;           // (++pass: 0 again; nothing has been emitted yet)
                 continue;
             }
-            if (s_full != 0u && tid == 0) atomicMax(&a.counters[CTR_BINFAIL], 1ull);
+            const qs_kargs_t kc = qs_cold_args();
+            if (s_full != 0u && tid == 0) atomicMax(&kc->a.counters[CTR_BINFAIL], 1ull);
+            const uint32_t gmin_c = kc->ga.g.gmin;
             // candidates: count >= the floor -> the query's buffer in LDS (its first SB_CAND), the rest to the shared list
             for (uint32_t s = tid; s < T; s += QS_WG) {
                 const unsigned long long e = table[s];
                 if (e == 0ull) continue;
-                const uint32_t count = (uint32_t)e, doc = (uint32_t)(e >> 32);
+                const uint32_t count = (uint32_t)e, doc = gmin_c + (uint32_t)(e >> 32);       // (the table's key is doc - gmin)
                 if (count < floor_q) continue;
-                if ((uint64_t)count > smax) atomicMax(&a.counters[CTR_MAXSCORE], (unsigned long long)count);
+                if ((uint64_t)count > smax) atomicMax(&kc->a.counters[CTR_MAXSCORE], (unsigned long long)count);
                 const uint64_t sc = (uint64_t)count > smax ? smax : (uint64_t)count;
-                const uint64_t qpart = a.sb >= 32u ? 0ull : ((uint64_t)q << (32u + a.sb));
+                const uint64_t qpart = sb >= 32u ? 0ull : ((uint64_t)q << (32u + sb));
                 const uint64_t key = qpart | ((smax - sc) << 32) | doc;
                 const uint32_t at = atomicAdd(&s_ccnt, 1u);
                 if (at < SB_CAND) cbuf[at] = key;
                 else {
-                    const unsigned long long gi = atomicAdd(&a.counters[CTR_CANDS], 1ull);
-                    if (gi < a.cand_cap) a.cands[gi] = key;
+                    const unsigned long long gi = atomicAdd(&kc->a.counters[CTR_CANDS], 1ull);
+                    if (gi < kc->a.cand_cap) kc->a.cands[gi] = key;
                     s_cshared = 1u;
                 }
             }
@@ -720,25 +777,26 @@ __global__ __launch_bounds__(QS_WG) FPX_QS_OCC void k_search_query(QSearchArgs a
     QS_MARK(4);
     const uint32_t cn = min(s_ccnt, SB_CAND);
     const bool shared = s_cshared != 0u || cn > QCAND_SLOTS;
+    const qs_kargs_t kh = qs_cold_args();
     if (tid == 0) {
         if (shared && cn != 0u) {
-            const unsigned long long gi = atomicAdd(&a.counters[CTR_CANDS], (unsigned long long)cn);
+            const unsigned long long gi = atomicAdd(&kh->a.counters[CTR_CANDS], (unsigned long long)cn);
             s_cbase_lo = (uint32_t)gi; s_cbase_hi = (uint32_t)(gi >> 32);
         }
-        a.qcand_n[q] = shared ? QCAND_OVERFLOWED : cn;
+        kh->a.qcand_n[q] = shared ? QCAND_OVERFLOWED : cn;
     }
     __syncthreads();
     if (tid < cn) {
         const uint64_t key = cbuf[tid];
-        if (!shared) a.qcand[(size_t)q * QCAND_SLOTS + tid] = key;
+        if (!shared) kh->a.qcand[(size_t)q * QCAND_SLOTS + tid] = key;
         else {
             const uint64_t gi = (((uint64_t)s_cbase_hi << 32) | s_cbase_lo) + tid;
-            if (gi < a.cand_cap) a.cands[gi] = key;
+            if (gi < kh->a.cand_cap) kh->a.cands[gi] = key;
         }
     }
     QS_MARK(5);
     if (!has_next) break;
-    if (tid == 0u) s_q2 = a.next_q != nullptr ? a.q_begin + 2u * gridDim.x + r2 : qn + gridDim.x;
+    if (tid == 0u) s_q2 = kh->a.next_q != nullptr ? a.q_begin + 2u * gridDim.x + r2 : qn + gridDim.x;
     q = qn; q_lo = nq_lo; n = nn; qh = a.hashes_base + nq_lo;
     __syncthreads();                                    // (the candidate buffer and the flags have been read: the next query may reset them)
     qn1 = s_q2;
