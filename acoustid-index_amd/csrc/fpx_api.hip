@@ -421,6 +421,7 @@ static const OptInfo OPT_TABLE[OPT_COUNT] = {
     /* OPT_SHARDED_WORKERS */    {"sharded_workers", "FPX_SHARDED_WORKERS", 3, 1, true},
     /* OPT_HOT_REFS */           {"hot_refs", "FPX_HOT_REFS", -1, -1, true},                     // 1 | 0 | -1: hot lists reach the score kernel by reference | are copied | by the last batch's records
     /* OPT_QUERY_WG */           {"query_wg", "FPX_QUERY_WG", 1, 0, false},                      // 1 | 0 | 2: a snapshot that is ONE packed group is searched a query per workgroup (fpx_qsearch.hpp) | by the keys - probe - bins - score pipeline | as 1, a group with superseded docs or masked columns too
+    /* OPT_SIDE_WG */            {"side_wg", "FPX_SIDE_WG", 0, 0, false},                        // 0 | 1: the file segments next to the group (small decoded, direct-addressed alone) by the pipeline | a query per workgroup (fpx_qside.hpp)
 };
 
 int64_t ctx_opt(const Ctx* c, CtxOpt o)

@@ -377,6 +377,7 @@ enum CtxOpt : int {
     OPT_SHARDED_WORKERS,
     OPT_HOT_REFS,
     OPT_QUERY_WG,
+    OPT_SIDE_WG,
     OPT_COUNT
 };
 constexpr int64_t OPT_UNSET = -2;

@@ -44,6 +44,7 @@
 #include "fpx_score.hpp"
 #include "fpx_score_bin.hpp"
 #include "fpx_qsearch.hpp"
+#include "fpx_qside.hpp"
 
 namespace fpx {
 
@@ -468,6 +469,27 @@ static int run_batch(Snapshot* snap, Workspace* ws, const QueryBatch* resident, 
         }
     }
 
+    // ---- ... and the same for the file segments NEXT TO the group (fpx_qside.hpp; option side_wg = 1): a snapshot -- part 1 of a live one, or a
+    //      whole young index -- of small decoded and direct-addressed-alone segments only, none of them a hash-window slice, no group, no
+    //      memory-segment postings.  The queries' rule is parts_take's, so a batch in two parts never splits between paths by query.
+    bool side_path = false;
+    if (!qs_path && !ex && !no_fast && !no_qs && !single_fast && B >= 2u && P != 0 && qb <= 24u && ctx_opt(snap->ctx, OPT_SIDE_WG) == 1 &&
+        snap->n_group == 0 && snap->n_lean == 0 && snap->n_gen == 0 && snap->n_file == snap->n_small && snap->n_direct == snap->n_solo &&
+        snap->n_small + snap->n_solo != 0 && (snap->n_mem == 0 || snap->mem_items == 0)) {
+        side_path = true;
+        for (const SegDesc& d : snap->h_file) side_path = side_path && d.own_flags == 0u && d.items && d.sbucket && d.sfirst && d.scode;
+        for (const SegDesc& d : snap->h_direct) side_path = side_path && d.own_flags == 0u && d.drec && d.primary;
+        for (uint32_t q = 0; q < B && side_path; ++q) {
+            const uint64_t raw_len = offsets[q + 1] - offsets[q];
+            side_path = raw_len <= QS_MAX_HASHES && (opts[q].has_min_score ? opts[q].min_score : (uint32_t)((raw_len + 19) / 20)) > 2u;
+        }
+        if (side_path) {
+            // (the back-off after a hand-back, as above: this snapshot's own count -- a part 1 is a snapshot of its own)
+            uint32_t skip = __atomic_load_n(&snap->qs_skip, __ATOMIC_RELAXED);
+            if (skip != 0u) { __atomic_store_n(&snap->qs_skip, skip - 1u, __ATOMIC_RELAXED); side_path = false; }
+        }
+    }
+
     uint32_t up_chunks = 0, up_q[Workspace::UP_CHUNKS + 1] = {0};      // (a chunked upload: the pieces' query ranges)
     auto upload_piece = [&](uint32_t c) -> int {                       // piece c of the batch's hashes, on the copy stream; its event behind it
         const uint64_t h0 = offsets[up_q[c]] - base, h1 = offsets[up_q[c + 1]] - base;
@@ -537,7 +559,7 @@ static int run_batch(Snapshot* snap, Workspace* ws, const QueryBatch* resident, 
     }
     // deferred-probe lists of the lean kernel: room for 1/8 of the pairs per segment (typically < 2 % are deferred)
     const size_t def_cap = std::max<size_t>(4096, (size_t)(P / 8));
-    if (snap->n_lean || snap->n_direct) {
+    if (snap->n_lean || snap->n_direct || side_path) {          // (k_search_side: the statistics sets behind the counts)
         const size_t need = def_cap * std::max(1u, snap->n_lean);
         if ((rc = grow(&ws->d_def_list, &ws->cap_def, need))) return rc;
         if (snap->n_lean > ws->cap_def_segs || !ws->d_def_count) {
@@ -571,14 +593,14 @@ static int run_batch(Snapshot* snap, Workspace* ws, const QueryBatch* resident, 
     const uint32_t key_skip = flagged ? KEY_SORT_SKIP_DIRECT : KEY_SORT_SKIP;      // (flagged keys: the top 8 hash bits -- 8 / 7 / 6 bits measured alike, 5 / 4 slower: round 5)
     // small batches sort their keys per query in ONE kernel (k_make_keys_sorted) instead of batch-wide in eleven launches
     const uint64_t local_sort_max = (uint64_t)std::max<int64_t>(0, ctx_opt(snap->ctx, OPT_LOCAL_SORT_MAX));
-    bool local_sort = P && !score_only && !single_fast && !flagged && !qs_path && B >= 2u && P <= local_sort_max && snap->n_small == 0;
+    bool local_sort = P && !score_only && !single_fast && !flagged && !qs_path && !side_path && B >= 2u && P <= local_sort_max && snap->n_small == 0;
     if (local_sort)
         for (uint32_t q = 0; q < B && local_sort; ++q) local_sort = offsets[q + 1] - offsets[q] <= QSORT_MAX;
     if (local_sort) {
         hipLaunchKernelGGL(k_make_keys_sorted, dim3(B), dim3(256), 0, st, d_hashes_base, d_offsets, B, qb, base, ws->d_keys[0],
                            (snap->n_lean || snap->n_direct) ? ws->d_def_count : nullptr, (uint32_t)def_words);
         FPX_HIP(hipGetLastError());
-    } else if (P && !score_only && !qs_path) {
+    } else if (P && !score_only && !qs_path && !side_path) {
         // flagged keys are brought into (hash bucket, query) order by our own counting sort, whose counts k_make_keys_dedup takes
         // on its way (fpx_keyorder.hpp); tiny batches stay in query order (the three launches cost what the order buys)
         const uint64_t order_min = (uint64_t)std::max<int64_t>(0, ctx_opt(snap->ctx, OPT_ORDER_MIN_PAIRS));
@@ -752,6 +774,94 @@ static int run_batch(Snapshot* snap, Workspace* ws, const QueryBatch* resident, 
             stats->probe_kernel_bytes += blocks * 512ull + bytes_off;
             stats->probe_kernel_fetched_bytes += (dreads + 1) / 2 * 128ull;
             stats->path_flags |= 1u | (Cf ? 2u : 0u) | 4u | 64u | (qs_filt ? 256u : 0u);
+        }
+        if ((rc = deliver_qstats())) return rc;
+        ws->hint_P = P; ws->hint_H = std::max<uint64_t>(records, 1);          // (sizes the pipeline's bins should a later batch take it)
+        ws->hint_misc = 0; ws->hint_def = 0;
+        return FPX_OK;
+    }
+    if (side_path) {
+        if ((rc = grow(&ws->d_qcand, &ws->cap_qcand, (size_t)B * QCAND_SLOTS + 2 * ((size_t)B / 2 + 1)))) return rc;
+        uint64_t* d_qcand = ws->d_qcand;
+        uint32_t* d_qcand_n = reinterpret_cast<uint32_t*>(ws->d_qcand + (size_t)B * QCAND_SLOTS);
+        const size_t cand_guess0 = std::max<size_t>(1u << 16, (size_t)B * 64);
+        if (ws->cap_cands < cand_guess0 && (rc = grow_pair(ws->d_cands, &ws->cap_cands, cand_guess0))) return rc;
+        const uint32_t sbf = 32u - qb;
+        hipLaunchKernelGGL(k_qs_zero, dim3(8), dim3(256), 0, st, ws->d_counters, ws->d_def_count, (uint32_t)def_words);
+        FPX_HIP(hipEventRecord(ws->ev_probe0, st));
+        SideArgs sa{};
+        sa.hashes_base = d_hashes_base; sa.offsets = d_offsets; sa.opts = d_opts; sa.B = B; sa.sb = sbf;
+        sa.cands = ws->d_cands[0]; sa.cand_cap = ws->cap_cands; sa.qcand = d_qcand; sa.qcand_n = d_qcand_n;
+        sa.counters = ws->d_counters; sa.stat_sets = reinterpret_cast<unsigned long long*>(ws->d_def_count + def_stat_off);
+        sa.qstats = want_q ? ws->d_qstats : nullptr; sa.cancel = cancel;
+        sa.small = snap->d_small; sa.n_small = snap->n_small; sa.solo = snap->d_solo; sa.n_solo = snap->n_solo;
+        // as many workgroups as the chip holds at once (LDS: SIDE_WGS_PER_CU per CU); each takes every gridDim.x-th query
+        static std::atomic<int> side_cus_of[64];             // (asked of the runtime once per device, as the block above does)
+        int cus = side_cus_of[(unsigned)snap->ctx->device & 63u].load(std::memory_order_relaxed);
+        if (cus == 0) {
+            if (hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, snap->ctx->device) != hipSuccess || cus <= 0) { (void)hipGetLastError(); cus = 256; }
+            side_cus_of[(unsigned)snap->ctx->device & 63u].store(cus, std::memory_order_relaxed);
+        }
+        hipLaunchKernelGGL(k_search_side, dim3(std::min<uint32_t>(B, (uint32_t)cus * SIDE_WGS_PER_CU)), dim3(SIDE_WG), SIDE_LDS_BYTES, st, sa);
+        FPX_HIP(hipGetLastError());
+        FPX_HIP(hipEventRecord(ws->ev_probe1, st));
+        fpx_result* d_res = partial ? out : ws->d_out;
+        uint32_t* d_res_n = partial ? out_n : ws->d_out_n;
+        bool staged = false;
+        if (!partial && (rc = staged_targets(ws, snap->ctx, B, out_cap, &staged, &d_res_n, &d_res))) return rc;
+        hipLaunchKernelGGL(k_finish, dim3((B + 127) / 128), dim3(128), 0, st,
+                           (const uint64_t*)ws->d_cands[0], (uint64_t)0, d_opts, B, sbf, partial ? 1 : 0, d_res, out_cap, d_res_n,
+                           (const uint64_t*)d_qcand, (const uint32_t*)d_qcand_n, stats ? ws->d_counters : nullptr);
+        {
+            PublishArgs pa{};
+            pa.counters = ws->d_counters; pa.h_counters = mapped_address(ws->h_counters);
+            pa.a_src = ws->d_def_count; pa.a_dst = mapped_address(ws->h_def_count); pa.a_n = (uint32_t)def_words;
+            if (!pa.h_counters || !pa.a_dst) { set_error("page-locked host memory is not mapped into the device"); return FPX_E_DEVICE; }
+            hipLaunchKernelGGL(k_publish, dim3(4), dim3(256), 0, st, pa);
+            FPX_HIP(hipGetLastError());
+        }
+        FPX_HIP(hipEventRecord(ws->ev_end, st));
+        FPX_SYNC(ws);
+        if (ws->h_counters[CTR_BINFAIL] != 0 || ws->h_counters[CTR_MAXSCORE] != 0 || ws->h_counters[CTR_CANDS] > ws->cap_cands) {
+            if (ws->h_counters[CTR_BINFAIL] != 0) __atomic_store_n(&snap->qs_skip, 32u, __ATOMIC_RELAXED);
+            return FPX_REDO_QS;                           // (that snapshot or part alone: run_with_redos)
+        }
+        uint64_t Cf = 0;
+        int ccur2 = 0;
+        if (ws->h_counters[CTR_CANDS] != 0) {
+            // some queries have more candidates than slots: sort the shared list and finish again (second round trip)
+            Cf = ws->h_counters[CTR_CANDS];
+            const size_t tb2 = sort_u64_temp_bytes(Cf, 0, 64);
+            if ((rc = grow(reinterpret_cast<uint8_t**>(&ws->d_temp), &ws->cap_temp, tb2 + 256))) return rc;
+            FPX_HIP(sort_u64(ws->d_temp, ws->cap_temp, ws->d_cands[0], ws->d_cands[1], Cf, 0, 64, st, &ccur2));
+            if (stats) FPX_HIP(hipMemsetAsync(&ws->d_counters[CTR_SLOTCANDS], 0, sizeof(unsigned long long), st));
+            hipLaunchKernelGGL(k_finish, dim3((B + 127) / 128), dim3(128), 0, st,
+                               (const uint64_t*)ws->d_cands[ccur2], Cf, d_opts, B, sbf, partial ? 1 : 0, d_res, out_cap, d_res_n,
+                               (const uint64_t*)d_qcand, (const uint32_t*)d_qcand_n, stats ? ws->d_counters : nullptr);
+            FPX_HIP(hipGetLastError());
+            FPX_HIP(hipMemcpyAsync(&ws->h_counters[CTR_SLOTCANDS], &ws->d_counters[CTR_SLOTCANDS], sizeof(unsigned long long), hipMemcpyDeviceToHost, st));
+            FPX_HIP(hipEventRecord(ws->ev_end, st));
+            FPX_SYNC(ws);
+        }
+        if (!partial && (rc = deliver_results(ws, B, out_cap, staged, out, out_n, st))) return rc;
+        const unsigned long long* ls = reinterpret_cast<const unsigned long long*>(ws->h_def_count + def_stat_off);
+        unsigned long long blocks = 0, docs = 0, probes = 0, dreads = 0, bytes_off = 0, records = 0;
+        for (uint32_t i = 0; i < LEAN_STAT_SETS; ++i) {
+            blocks += ls[i * 8 + 1]; docs += ls[i * 8 + 2]; probes += ls[i * 8 + 3]; dreads += ls[i * 8 + 4];
+            bytes_off += ls[i * 8 + 5]; records += ls[i * 8 + 7];
+        }
+        gather_hist(ws->batch_hist, ws->h_counters, ls, probes);
+        if (stats) {
+            float ms = 0.f, total_ms = 0.f;
+            (void)hipEventElapsedTime(&ms, ws->ev_probe0, ws->ev_probe1);
+            (void)hipEventElapsedTime(&total_ms, ws->ev_begin, ws->ev_end);
+            stats->probes += probes; stats->scanned_blocks += blocks; stats->scanned_docs += docs; stats->hits += records;
+            stats->algorithmic_bytes += blocks * 512ull + bytes_off;
+            stats->candidates += Cf + ws->h_counters[CTR_SLOTCANDS];
+            stats->probe_kernel_ms += ms; stats->total_gpu_ms += total_ms; stats->probe_launches += 1;
+            stats->probe_kernel_bytes += blocks * 512ull + bytes_off;
+            stats->probe_kernel_fetched_bytes += (dreads + 1) / 2 * 128ull;
+            stats->path_flags |= 1u | (Cf ? 2u : 0u) | 512u;
         }
         if ((rc = deliver_qstats())) return rc;
         ws->hint_P = P; ws->hint_H = std::max<uint64_t>(records, 1);          // (sizes the pipeline's bins should a later batch take it)

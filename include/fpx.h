@@ -85,7 +85,9 @@ typedef struct {
                                    per workgroup, the file segments next to it by the pipeline, the two tables merged (a live index
                                    between merges: fpx_snapshot_create),
                                    bit 8: the batch (or its part 0) ran the FILTERED k_search_query: a packed group with superseded
-                                   docs and/or columns outside the snapshot, searched a query per workgroup ("query_wg" 2) */
+                                   docs and/or columns outside the snapshot, searched a query per workgroup ("query_wg" 2),
+                                   bit 9: the batch (or its part 1) ran k_search_side: the file segments next to the group -- small decoded
+                                   ones, direct-addressed ones on their own -- searched a query per workgroup ("side_wg" 1) */
     uint64_t probe_kernel_fetched_bytes; /* block bytes the main probe kernel really fetched, in 128-byte lines: a probe
                                    whose hash the segment's presence bits know to be absent counts as a visited block (as in
                                    the reference) without the block being read, and a block that is read costs two lines up
@@ -116,6 +118,12 @@ int  fpx_ctx_device(const fpx_ctx *ctx);     /* the HIP ordinal the context live
  *                        (csrc/fpx_qsearch.hpp; default 1) | by the pipeline below like every other snapshot | as 1, and so is a
  *                        packed group with superseded docs and/or columns outside the snapshot (a live index after updates, deletes
  *                        or a merge without regroup), by the kernel's filtered form (fpx_stats.path_flags bit 8)
+ *   "side_wg"            0 | 1   the file segments NEXT TO the group of a live index -- part 1 of a snapshot in two parts, or a whole
+ *                        young index: small decoded segments and direct-addressed ones on their own, no hash-window slice -- are searched
+ *                        by the pipeline below (default 0) | a QUERY PER WORKGROUP (csrc/fpx_qside.hpp; fpx_stats.path_flags bit 9), for
+ *                        batches of queries k_search_query would take (up to 4096 hashes, a floor above 2); a query whose records
+ *                        outgrow the workgroup's array hands that snapshot or part back to the pipeline -- and the next 32 batches of
+ *                        that snapshot (or part) stay on the pipeline without trying, bit 9 clear: hot-hash traffic comes in runs
  *   "fast"               1 | 0   the device-sized path (one host round trip per batch; default 1)
  *   "binned"             1 | 0   groups drop their records into bins of a few queries, scored a bin per workgroup (default 1)
  *   "rec32"              1 | 0   4-byte records in the bins where the doc ids leave room (default 1)

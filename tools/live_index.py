@@ -5,7 +5,11 @@ segments, src/Index.zig:679-687: 0.5 M items each, decoded next to their blocks)
 on its own).  One batch of 8192 x 1000 in flight, resident; every 16th query aims at a doc of one of the additions and must find it.
 One JSON line per snapshot shape: ms per step, the path the batches took (fpx_stats.path_flags), targets found.
 
-    DOCS=100000000 python tools/live_index.py            (gpurun: ~2 min)"""
+    DOCS=100000000 python tools/live_index.py            (~2 min)
+    SIDE_AB=4 SHAPES=1,4 DOCS=100000000 python tools/live_index.py
+        ... and each shape again under option side_wg 0 and 1 (csrc/fpx_qside.hpp), alternating, four runs each in this process: one JSON
+        line per run -- ms per step, the GPU time of the whole call (part 0 + part 1) and, for a shape with file segments next to the group, what
+        is left of it for part 1 once the GPU time of the shape's part 0 (the group + its memory segments, timed on its own) is taken off"""
 import json
 import os
 import sys
@@ -105,6 +109,31 @@ def main():
         print(json.dumps({"snapshot": label, "ms_per_step": round(dt / steps * 1e3, 4), "queries_per_s": round(B * steps / dt),
                           "gpu_ms_per_step": round(agg.v["total_gpu_ms"] / steps, 4), "callers": nfl, "ms_per_step_with_callers": round(dt_m / (steps * nfl) * 1e3, 4), "queries_per_s_with_callers": round(B * steps * nfl / dt_m), "snapshot_create_ms": round(snap_ms, 2), "snapshot_create_again_ms": round(snap_again_ms, 2), "path_flags": agg.path_flags, "targets_found": found, "of": B,
                           "info": {k: v for k, v in snap.info().items() if k in ("lean", "generic", "small", "direct_solo", "groups", "packed_groups", "memory")}}), flush=True)
+        n_ab = int(os.environ.get("SIDE_AB", 0))
+        files = [e for e in extra if not any(e is m for m in mems)]   # the shape's file segments next to the group: its part 1
+        part0_gpu_ms = None
+        if n_ab and files:
+            # part 0 of this shape on its own -- the group + the shape's memory segments --, timed here with the same batches: what is left of the
+            # whole call's GPU time is part 1's (+ k_merge)
+            snap0 = fpx.Segments(ctx, list(segs) + [e for e in extra if any(e is m for m in mems)])
+            reader0 = fpx.IndexReader(snap0)
+            _, agg0, _, _ = bench.timed_resident(fpx, reader0, qbs, steps, 8)
+            part0_gpu_ms = agg0.v["total_gpu_ms"] / steps
+            snap0.release()
+            del reader0, snap0
+        for r in range(2 * n_ab):         # side_wg 0, 1, 0, 1, ...: the file segments next to the group by the pipeline | a query per workgroup
+            ctx.set_option("side_wg", r % 2)
+            try:
+                dt_a, agg_a, out_a, out_n_a = bench.timed_resident(fpx, reader, qbs, steps, 8)
+            finally:
+                ctx.set_option("side_wg", -1)
+            last_a = qs[(8 + steps - 1) % len(qs)]
+            gpu_a = agg_a.v["total_gpu_ms"] / steps
+            print(json.dumps({"snapshot": label, "side_wg": r % 2, "run": r // 2, "ms_per_step": round(dt_a / steps * 1e3, 4), "gpu_ms_per_step": round(gpu_a, 4),
+                              "part0_gpu_ms_per_step": None if part0_gpu_ms is None else round(part0_gpu_ms, 4),
+                              "part1_gpu_ms_per_step": None if part0_gpu_ms is None else round(gpu_a - part0_gpu_ms, 4),
+                              "probe_kernel_ms_per_step": round(agg_a.v["probe_kernel_ms"] / steps, 4), "path_flags": agg_a.path_flags,
+                              "targets_found": int(sum(1 for q in range(B) if out_n_a[q] > 0 and out_a[q, 0, 0] == last_a[2][q])), "of": B}), flush=True)
         for q_ in qbs:
             q_.release()
         snap.release()
