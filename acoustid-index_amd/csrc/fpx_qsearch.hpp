@@ -141,8 +141,19 @@ __device__ __forceinline__ uint32_t qs_word_cols(uint32_t pm, uint32_t dm, uint3
 // counters [16 ..], which the host prints; tools/build_variant.sh qs_prof -DFPX_QS_PROF=1)
 #ifdef FPX_QS_PROF
 #define QS_MARK(i) do { if (tid == 0) { const unsigned long long t_ = clock64(); atomicAdd(&qs_cold_args()->a.counters[CTR_HIST + (i)], t_ - t_prev); t_prev = t_; } } while (0)
+// (finer marks inside a phase, slots [6 ..]: QS_SUB0 starts a stretch, QS_SUB(i) adds the clocks since the last of either to slot i; QS_ARRIVED
+// makes every wave wait right there for the loads whose values it names -- the stretch behind it is that wait and nothing else.  The waits
+// and the marks' own atomics stretch a query by half: the finer clocks compare builds, they are not shares of the product's time)
+#define QS_SUB0() do { if (tid == 0) t_sub = clock64(); } while (0)
+#define QS_SUB(i) do { if (tid == 0) { const unsigned long long t_ = clock64(); atomicAdd(&qs_cold_args()->a.counters[CTR_HIST + (i)], t_ - t_sub); t_sub = t_; } } while (0)
+#define QS_ARRIVED2(x, y) asm volatile("" :: "v"(x), "v"(y))
+#define QS_ARRIVED4(x) asm volatile("" :: "v"((x)[0]), "v"((x)[1]), "v"((x)[2]), "v"((x)[3]))
 #else
 #define QS_MARK(i) do { } while (0)
+#define QS_SUB0() do { } while (0)
+#define QS_SUB(i) do { } while (0)
+#define QS_ARRIVED2(x, y) do { } while (0)
+#define QS_ARRIVED4(x) do { } while (0)
 #endif
 // (MEM: the snapshot has memory segments -- an instantiation of its own: their look-up costs the usual one registers.  FILT: the group has
 // superseded docs and/or columns outside the snapshot -- the supersession filter and the column masks, ga.segs' dead sets)
@@ -150,7 +161,7 @@ template <int NS, bool QS, bool MEM, bool FILT>
 __global__ __launch_bounds__(QS_WG) FPX_QS_OCC void k_search_query(QSearchArgs a, GroupArgs ga)
 {
 #ifdef FPX_QS_PROF
-    unsigned long long t_prev = clock64();
+    unsigned long long t_prev = clock64(), t_sub = 0;
 #endif
     constexpr uint32_t HVL = NS == 16 ? 2u : 3u;        // log2 of the hash values per line
     constexpr uint32_t T = 1u << QS_TLOG2, TMASK = T - 1u;
@@ -173,13 +184,21 @@ __global__ __launch_bounds__(QS_WG) FPX_QS_OCC void k_search_query(QSearchArgs a
     const uint32_t tid = threadIdx.x, lane = tid & 63u;
     const GroupDesc* g = &ga.g;
     // The workgroup STAYS: it takes query blockIdx.x, then blockIdx.x + gridDim.x, then what the launch's counter hands out (the host launches as
-    // many workgroups as the chip holds at once; a workgroup that starts late -- behind another batch's kernel -- or draws long queries takes fewer).  What a query's start waits for -- its offsets, its hashes, the heads of its first lines: three latencies in a row -- is
-    // asked for while the query before it is still being counted.
+    // many workgroups as the chip holds at once; a workgroup that starts late -- behind another batch's kernel -- or draws long queries takes fewer).
+    // What a query's start waits for -- its offsets, then its hashes: two latencies in a row, the second one HBM's -- is asked for while
+    // the queries before it are at work: the offsets of the query after the next one as soon as the counter has named it (under this query's
+    // counting), the next query's hashes -- the first four rounds' at once -- under this query's tasks and counting.
     uint32_t q = a.q_begin + blockIdx.x;
-    uint32_t qn1 = q + gridDim.x;                       // the query after this one
-    uint64_t q_lo = a.offsets[q];
-    uint32_t n = (uint32_t)(a.offsets[q + 1] - q_lo);
-    const uint32_t* qh = a.hashes_base + q_lo;
+    uint32_t qn = q + gridDim.x;                        // the query after this one ...
+    uint32_t n, nn = 0u;
+    uint64_t nq_lo = 0;                                 // ... and where its hashes are (nn of them)
+    const uint32_t* qh;
+    {
+        const uint64_t q_lo = a.offsets[q];
+        n = (uint32_t)(a.offsets[q + 1] - q_lo);
+        qh = a.hashes_base + q_lo;
+        if (qn < a.q_end) { nq_lo = a.offsets[qn]; nn = (uint32_t)(a.offsets[qn + 1] - nq_lo); }
+    }
     {
         const qs_kargs_t ka = qs_cold_args();
         if (tid < FUSE_MAX) { s_first[tid] = ka->ga.g.first_hash[tid]; s_last[tid] = ka->ga.g.last_hash[tid]; }
@@ -190,28 +209,43 @@ __global__ __launch_bounds__(QS_WG) FPX_QS_OCC void k_search_query(QSearchArgs a
     // supersession test (FILT) and the memory segments' absolute docs (MEM) need it before that)
     const uint32_t gmin = (FILT || MEM) ? g->gmin : 0u;
     (void)gmin;
-    // ---- the first QS_CH rounds' hashes and the heads of their lines (position bits, double flags) set out at once: a round is a chain
-    //      of latencies -- hash, line head (HBM), words, ... -- and a CU holds sixteen waves to overlap them; what does not depend on the
-    //      round before it is asked for up front.  (A duplicate's line is fetched for nothing: dedup runs while the heads travel.)
-    uint32_t hh[QS_CH];
+    // ---- a query's hashes are read ONCE, into registers, before the query starts: hq[] holds the lane's hashes of two pairs of rounds --
+    //      the whole query up to 1024 hashes.  Dedup reads them there and so do the rounds (nobody else has touched those lines of the
+    //      batch's hash array: read where they are needed they are a miss in HBM with the whole workgroup waiting, then a trip to the L2
+    //      again in front of the second pair's heads).  A longer query's later pairs follow a pair ahead: in dedup into nx[] while the pair
+    //      before is inserted, in the rounds into hq[2..3] while hq[0..1] are probed -- the window rolls (static indices: no scratch).
+    //      The heads of a pair's lines (position bits, double flags) are asked for at the top of its rounds, after dedup, both at once: a
+    //      duplicate's line and a hash outside the window are not fetched at all.
+    uint32_t hq[2u * QS_CH];
     uint3 hd[QS_CH];
     auto line_of = [&](uint32_t h) -> const uint32_t* { return g->lines + (size_t)((h >> HVL) - g->line0) * GROUP_LINE_WORDS; };
-    auto load_hashes = [&](uint32_t c) {
-#pragma unroll
-        for (uint32_t u = 0; u < QS_CH; ++u) {
-            const uint32_t i = (c * QS_CH + u) * QS_WG + tid;
-            hh[u] = i < n ? gload_u32(qh + i) : 0u;
+    // (the lane's hashes of pair c of a query of n_ hashes at qh_)
+    auto load_pair = [&](const uint32_t* qh_, uint32_t n_, uint32_t c, uint32_t& h0, uint32_t& h1) {
+        const uint32_t i = c * QS_CH * QS_WG + tid;
+        h0 = i < n_ ? gload_u32(qh_ + i) : 0u;
+        h1 = i + QS_WG < n_ ? gload_u32(qh_ + i + QS_WG) : 0u;
+    };
+    // (of the pair in hq[0..1]; v0, v1: which of the two are probes.  A lane without a probe reads the group's first line, which nobody
+    // looks at -- one address per wave, a hit in the L2 --: a load under a branch comes with its unpacking and the wait for it inside the
+    // branch, and the pair's two trips to HBM would follow one another)
+    auto issue_heads = [&](bool v0, bool v1) {
+        hd[0] = gload_u3(v0 ? line_of(hq[0]) : g->lines);
+        hd[1] = gload_u3(v1 ? line_of(hq[1]) : g->lines);
+    };
+    load_pair(qh, n, 0u, hq[0], hq[1]);
+    load_pair(qh, n, 1u, hq[2], hq[3]);
+    // (the cancel flag as lane 0 sees it, asked for a query ahead like the rest: cancel_requested() in two halves)
+    uint32_t c_host = 0u;
+    unsigned long long c_dev = 0ull;
+    auto ask_cancel = [&]() {
+        const qs_kargs_t ka = qs_cold_args();
+        const uint32_t* const cancel = ka->a.cancel;
+        if (tid == 0u && cancel != nullptr) {
+            if ((blockIdx.x & 63u) == 0u) c_host = __hip_atomic_load(cancel, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
+            c_dev = __hip_atomic_load(&ka->a.counters[CTR_CANCEL], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
         }
     };
-    auto issue_heads = [&](uint32_t c) {
-#pragma unroll
-        for (uint32_t u = 0; u < QS_CH; ++u) {
-            const uint32_t i = (c * QS_CH + u) * QS_WG + tid;
-            hd[u] = make_uint3(0u, 0u, 0u);
-            if (i < n && hh[u] >= g->win_lo && hh[u] <= g->win_hi) hd[u] = gload_u3(line_of(hh[u]));
-        }
-    };
-    load_hashes(0u);
+    ask_cancel();
   // Queries of one length keep a CU's four workgroups in LOCKSTEP -- all four in their rounds (the memory system's turn), then all four counting
   // (the LDS's and the VALU's) --: the workgroups of the chip's second, third and fourth wave of residents start a few microseconds apart
   // (s_sleep 127 = 3.4 us, `slot` times).  Measured, one batch of 8192 x 1000 in flight: 0.445 -> 0.430 ms (0.426 with twice the delay, 0.431 with four
@@ -232,8 +266,9 @@ __global__ __launch_bounds__(QS_WG) FPX_QS_OCC void k_search_query(QSearchArgs a
     if (tid == 0) {
         s_count = 0u; s_ntask = 0u; s_over_recs = 0u; s_seen_ones = 0u; s_ccnt = 0u; s_cshared = 0u;
         wg_blocks = 0; wg_docs = 0; wg_probes = 0; wg_reads = 0;
-        const qs_kargs_t ka = qs_cold_args();
-        s_cancel = cancel_requested(ka->a.cancel, ka->a.counters) ? 1u : 0u;  // cancel point (src/FileSegment.zig:144), once per query
+        // cancel point (src/FileSegment.zig:144), once per query, before its first probe: what ask_cancel() read
+        if (c_host != 0u) { atomicExch(&qs_cold_args()->a.counters[CTR_CANCEL], 1ull); c_dev = 1ull; }
+        s_cancel = c_dev != 0ull ? 1u : 0u;
     }
     __syncthreads();
     if (s_cancel) return;
@@ -242,14 +277,14 @@ __global__ __launch_bounds__(QS_WG) FPX_QS_OCC void k_search_query(QSearchArgs a
     //      which of its rounds' hashes are probes (a hash-window slice of the group leaves the other hashes to another rank)
     uint32_t vmask = 0u;
     uint32_t mmask = 0u;                                // (MEM) ... and which of them the memory segments' table may hold: a bit per 256 hash values
+    uint32_t nx[QS_CH] = {0u, 0u};                      // (a query of more than 1024 hashes: the pair after the one being inserted)
     for (uint32_t c = 0; c < nchunks; ++c) {
         uint32_t hc[QS_CH];
         uint32_t mb[QS_CH];
 #pragma unroll
-        for (uint32_t u = 0; u < QS_CH; ++u) {
-            const uint32_t i = (c * QS_CH + u) * QS_WG + tid;
-            hc[u] = c == 0u ? hh[u] : (i < n ? gload_u32(qh + i) : 0u);
-        }
+        for (uint32_t u = 0; u < QS_CH; ++u) hc[u] = c == 0u ? hq[u] : c == 1u ? hq[QS_CH + u] : nx[u];       // (uniform)
+        if (c != 0u) { QS_SUB0(); QS_ARRIVED2(hc[0], hc[1]); QS_SUB(6); }
+        if (c != 0u && c + 1u < nchunks) load_pair(qh, n, c + 1u, nx[0], nx[1]);
         if constexpr (MEM) {                            // (their bit words travel under the set's compare-and-swaps)
 #pragma unroll
             for (uint32_t u = 0; u < QS_CH; ++u) {
@@ -367,7 +402,9 @@ __global__ __launch_bounds__(QS_WG) FPX_QS_OCC void k_search_query(QSearchArgs a
     // there: the line is still in the L2 then.  Asked for a few rounds later -- round 6's first form fetched all heads up front -- the line
     // had been evicted and was fetched from memory AGAIN: 2.27 requests per query hash, profiles/r06_bench.json)
     // (... and what the walk needs of the head's arithmetic, packed: start | mine << 7 | nwords << 11 | inl << 17, and pm | dm << 16)
-    auto words_of = [&](uint32_t h, uint3 head, bool valid, uint32_t (&gw)[QS_WORDS], uint32_t& hx, uint32_t& hy) {
+    // (ov: where the hash's words run past the line's inline part, the offset of the rest in `ext` -- the line's last word -- travels
+    // with the words: probe forms its overflow tasks' address from a register)
+    auto words_of = [&](uint32_t h, uint3 head, bool valid, uint32_t (&gw)[QS_WORDS], uint32_t& hx, uint32_t& hy, uint32_t& ov) {
         const uint64_t bits = valid ? (((uint64_t)head.y << 32) | head.x) : 0ull;
         const uint32_t dfl = valid ? head.z : 0u;
         const uint32_t sh = (h & ((1u << HVL) - 1u)) * (uint32_t)NS;
@@ -391,10 +428,11 @@ __global__ __launch_bounds__(QS_WG) FPX_QS_OCC void k_search_query(QSearchArgs a
                 gw[4 * i] = v.x; gw[4 * i + 1] = v.y; gw[4 * i + 2] = v.z; gw[4 * i + 3] = v.w;
             }
         }
+        ov = start + nwords > inl ? gload_u32(line_of(h) + (GROUP_LINE_WORDS - 1u)) : 0u;
         hx = start | (mine << 7) | (nwords << 11) | (inl << 17);          // (start <= 96, mine <= 12, nwords <= 32, inl <= 29)
         hy = pm | (dm << 16);
     };
-    auto probe = [&](uint32_t h, uint32_t hx, uint32_t hy, bool valid, uint32_t (&gw)[QS_WORDS]) {
+    auto probe = [&](uint32_t h, uint32_t hx, uint32_t hy, bool valid, uint32_t (&gw)[QS_WORDS], uint32_t ov) {
         if (valid) { my_probes += nactive; my_reads += 2u; }
         const uint32_t pm = hy & 0xFFFFu, dm = hy >> 16;
         const uint32_t start = hx & 127u, mine = (hx >> 7) & 15u, nwords = (hx >> 11) & 63u, inl = (hx >> 17) & 31u;
@@ -485,9 +523,9 @@ __global__ __launch_bounds__(QS_WG) FPX_QS_OCC void k_search_query(QSearchArgs a
                 put_words(qs_task_words(line_of(h) + 3u + start + j, c, second >> j, chunk), j, c);
                 j += c;
             }
-            // ... and behind its end, in `ext` at the offset the line's last word holds
+            // ... and behind its end, in `ext` at the offset the line's last word holds (ov: words_of asked for it)
             if (j < nwords) {
-                const uint32_t* ob = ext + gload_u32(line_of(h) + (GROUP_LINE_WORDS - 1u));
+                const uint32_t* ob = ext + ov;
                 while (j < nwords) {                     // (start + j >= inl here)
                     const uint32_t c = min(nwords - j, QS_TASK_WORDS);
                     put_words(qs_task_words(ob + (start + j - inl), c, second >> j, chunk), j, c);
@@ -500,15 +538,29 @@ __global__ __launch_bounds__(QS_WG) FPX_QS_OCC void k_search_query(QSearchArgs a
 
     static_assert(QS_CH == 2, "the rounds run in pairs");
     for (uint32_t c = 0; c < nchunks; ++c) {
-        // two rounds at a time: their line heads, then -- as the heads arrive -- the words of both, then both rounds out of registers
-        if (c != 0u) load_hashes(c);
-        issue_heads(c);
+        // two rounds at a time, their hashes in hq[0..1]: their line heads, then -- as the heads arrive -- the words of both (and the offset
+        // of an overflowing line's rest), then both rounds out of registers
+        QS_SUB0();
+        QS_ARRIVED2(hq[0], hq[1]);
+        QS_SUB(7);
         const bool v0 = ((vmask >> (c * QS_CH)) & 1u) != 0u, v1 = ((vmask >> (c * QS_CH + 1u)) & 1u) != 0u;
+        issue_heads(v0, v1);
+        // (BOTH heads are under way before either is looked at: what follows sees the six words only behind this point)
+        asm volatile("" : "+v"(hd[0].x), "+v"(hd[0].y), "+v"(hd[0].z), "+v"(hd[1].x), "+v"(hd[1].y), "+v"(hd[1].z));
+        QS_SUB(8);
         uint32_t gw0[QS_WORDS], gw1[QS_WORDS], hx0, hy0, hx1, hy1;
-        words_of(hh[0], hd[0], v0, gw0, hx0, hy0);
-        words_of(hh[1], hd[1], v1, gw1, hx1, hy1);
-        probe(hh[0], hx0, hy0, v0, gw0);
-        if (c * QS_CH + 1u < rounds) probe(hh[1], hx1, hy1, v1, gw1);                    // (uniform)
+        uint32_t ov0, ov1;
+        words_of(hq[0], hd[0], v0, gw0, hx0, hy0, ov0);
+        words_of(hq[1], hd[1], v1, gw1, hx1, hy1, ov1);
+        asm volatile("" : "+v"(ov0), "+v"(ov1));             // (likewise: the second hash's words set out before the first one's offset is waited for)
+        QS_ARRIVED4(gw0); QS_ARRIVED4(gw0 + 4); QS_ARRIVED4(gw0 + 8); QS_ARRIVED4(gw1); QS_ARRIVED4(gw1 + 4); QS_ARRIVED4(gw1 + 8);
+        QS_SUB(9);
+        probe(hq[0], hx0, hy0, v0, gw0, ov0);
+        if (c * QS_CH + 1u < rounds) probe(hq[1], hx1, hy1, v1, gw1, ov1);              // (uniform)
+        QS_SUB(10);
+        // (the window rolls: the next pair moves up, the one after it -- a query of more than 1024 hashes -- sets out)
+        hq[0] = hq[2]; hq[1] = hq[3];
+        if (c + 2u < nchunks) load_pair(qh, n, c + 2u, hq[2], hq[3]);
     }
     // ---- MemorySegment.search (src/MemorySegment.zig:44-54) for all memory segments at once: the query's probes looked up in the snapshot's
     //      table of their live postings -- a bit per 256 hash values says "nothing there" for nine probes in ten --, four rounds' loads out
@@ -539,19 +591,26 @@ __global__ __launch_bounds__(QS_WG) FPX_QS_OCC void k_search_query(QSearchArgs a
     }
     __syncthreads();
     QS_MARK(2);
-    // ---- the NEXT query's offsets and hashes set out now (the chunk registers are free): they travel under this query's tasks and counting
-    // (... and the query after THAT is asked of the launch's counter: the answer has the tasks and the counting to arrive in)
+    // ---- the NEXT query's hashes set out now (the hash registers are free; its offsets have been here since the query before this one):
+    //      they travel under this query's tasks and counting
+    // (... and the query after THAT is asked of the launch's counter: the answer has the tasks to arrive in)
     uint32_t r2 = 0u;
     if (tid == 0u) { unsigned int* const next_q = qs_cold_args()->a.next_q; if (next_q != nullptr) r2 = atomicAdd(next_q, 1u); }
-    const uint32_t qn = qn1;
     const bool has_next = qn < a.q_end;                      // (uniform)
-    uint64_t nq_lo = 0; uint32_t nn = 0;
+    QS_SUB0();
+    QS_ARRIVED2(nn, (uint32_t)nq_lo); QS_SUB(11);
+    // (this query's floor, which the exact pass will want: every lane asks for the one word -- a vector load stays in flight
+    // under the LDS work, a scalar one would be waited for with the next LDS read)
+    uint32_t floor_v;
+    {
+        uint32_t qv = q;
+        asm volatile("" : "+v"(qv));
+        floor_v = gload_u32(qs_cold_args()->a.opts + (size_t)qv * 4u + 1u);
+    }
     if (has_next) {
-        nq_lo = a.offsets[qn]; nn = (uint32_t)(a.offsets[qn + 1] - nq_lo);
-        const uint32_t n_keep = n; const uint32_t* qh_keep = qh;
-        n = nn; qh = a.hashes_base + nq_lo;
-        load_hashes(0u);
-        n = n_keep; qh = qh_keep;
+        const uint32_t* const qhn = a.hashes_base + nq_lo;
+        load_pair(qhn, nn, 0u, hq[0], hq[1]);
+        load_pair(qhn, nn, 1u, hq[2], hq[3]);
     }
     // ---- the deferred tasks, a task per lane: every list head and overflow piece of the query is asked for at once.  (A list inside
     //      overflowing words is a task of the next pass.)
@@ -661,6 +720,8 @@ __global__ __launch_bounds__(QS_WG) FPX_QS_OCC void k_search_query(QSearchArgs a
         };
         const unsigned long long w_reads = wave_total(my_reads), w_blocks = wave_total(my_blocks), w_docs = wave_total(my_docs), w_probes = wave_total(my_probes & 0xFFFFu);
         const uint32_t w_doubles = (uint32_t)wave_total(my_probes >> 16);
+        // (the counter's answer -- the query after the next one -- goes to the workgroup behind the barrier below)
+        if (tid == 0u) s_q2 = qs_cold_args()->a.next_q != nullptr ? a.q_begin + 2u * gridDim.x + r2 : qn + gridDim.x;
         if (lane == 0u) {
             if (w_doubles) atomicAdd(&wg_h[0], w_doubles);
             if (w_reads) atomicAdd(&wg_reads, w_reads);
@@ -671,6 +732,18 @@ __global__ __launch_bounds__(QS_WG) FPX_QS_OCC void k_search_query(QSearchArgs a
     }
     __syncthreads();                                    // (the records are complete, the filter and the table are clear)
     QS_MARK(3);
+    // ---- the offsets of the query after the next one set out as soon as it is known, and the next query's cancel flag: they travel under
+    //      this query's counting (vector loads of one address, as the floor's above)
+    const uint32_t q2 = (uint32_t)__builtin_amdgcn_readfirstlane((int)s_q2);
+    const bool has_q2 = has_next && q2 < a.q_end;           // (uniform)
+    uint64_t o2_lo = 0;
+    uint32_t o2_hi = 0u;                                    // (the low word of its end: a query is shorter than 2^32 hashes)
+    if (has_q2) {
+        uint32_t qv = q2;
+        asm volatile("" : "+v"(qv));
+        o2_lo = gload_u64(a.offsets + qv); o2_hi = gload_u32(reinterpret_cast<const uint32_t*>(a.offsets + qv + 1u));
+    }
+    if (has_next) ask_cancel();
     const uint32_t nrec = min(s_count, QS_REC_CAP);
     // ---- SearchResults.incr (src/common.zig:121-129), first the filter: every record into its doc's cell
     // (four records per lane and turn, read as one 16-byte piece: the loop is a chain of LDS latencies -- a record, then its cell)
@@ -702,7 +775,7 @@ __global__ __launch_bounds__(QS_WG) FPX_QS_OCC void k_search_query(QSearchArgs a
     }
     // ---- ... then the floor of finish (src/common.zig:131-145): a doc can only reach the floor if its cell did; those records are
     //      counted exactly, in `passes` loads over classes of them when they are more than the table takes
-    const uint32_t floor_q = kt->a.opts[q * 4u + 1u];
+    const uint32_t floor_q = (uint32_t)__builtin_amdgcn_readfirstlane((int)floor_v);
     const uint32_t sb = kt->a.sb;
     const uint64_t smax = sb >= 32u ? 0xFFFFFFFFull : ((1ull << sb) - 1ull);
     if (s_over_recs == 0u && nrec != 0u && nrec >= floor_q) {
@@ -796,10 +869,13 @@ __global__ __launch_bounds__(QS_WG) FPX_QS_OCC void k_search_query(QSearchArgs a
     }
     QS_MARK(5);
     if (!has_next) break;
-    if (tid == 0u) s_q2 = kh->a.next_q != nullptr ? a.q_begin + 2u * gridDim.x + r2 : qn + gridDim.x;
-    q = qn; q_lo = nq_lo; n = nn; qh = a.hashes_base + nq_lo;
+    q = qn; n = nn; qh = a.hashes_base + nq_lo;
+    qn = q2; nn = 0u; nq_lo = 0;
+    if (has_q2) {
+        nq_lo = ((uint64_t)(uint32_t)__builtin_amdgcn_readfirstlane((int)(uint32_t)(o2_lo >> 32)) << 32) | (uint32_t)__builtin_amdgcn_readfirstlane((int)(uint32_t)o2_lo);
+        nn = (uint32_t)__builtin_amdgcn_readfirstlane((int)(o2_hi - (uint32_t)o2_lo));
+    }
     __syncthreads();                                    // (the candidate buffer and the flags have been read: the next query may reset them)
-    qn1 = s_q2;
   }
 }
 

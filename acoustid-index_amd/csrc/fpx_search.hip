@@ -731,8 +731,12 @@ static int run_batch(Snapshot* snap, Workspace* ws, const QueryBatch* resident, 
         FPX_HIP(hipEventRecord(ws->ev_end, st));
         FPX_SYNC(ws);
 #ifdef FPX_QS_PROF
-        fprintf(stderr, "qs_prof clocks/query: setup %.0f dedup %.0f rounds %.0f tasks %.0f count+exact %.0f handover %.0f\n", ws->h_counters[CTR_HIST] / (double)B, ws->h_counters[CTR_HIST + 1] / (double)B,
+        fprintf(stderr, "qs_prof clocks/query: setup %.0f dedup %.0f rounds %.0f tasks %.0f count+exact %.0f handover %.0f", ws->h_counters[CTR_HIST] / (double)B, ws->h_counters[CTR_HIST + 1] / (double)B,
                 ws->h_counters[CTR_HIST + 2] / (double)B, ws->h_counters[CTR_HIST + 3] / (double)B, ws->h_counters[CTR_HIST + 4] / (double)B, ws->h_counters[CTR_HIST + 5] / (double)B);
+        // (the finer marks: waits inside dedup, the rounds and before the tasks)
+        fprintf(stderr, " | dedup: hash wait %.0f | rounds: hash wait %.0f heads wait %.0f words wait %.0f probe %.0f | next offsets wait %.0f\n", ws->h_counters[CTR_HIST + 6] / (double)B,
+                ws->h_counters[CTR_HIST + 7] / (double)B, ws->h_counters[CTR_HIST + 8] / (double)B, ws->h_counters[CTR_HIST + 9] / (double)B, ws->h_counters[CTR_HIST + 10] / (double)B,
+                ws->h_counters[CTR_HIST + 11] / (double)B);
 #endif
         if (ws->h_counters[CTR_BINFAIL] != 0 || ws->h_counters[CTR_MAXSCORE] != 0 || ws->h_counters[CTR_CANDS] > ws->cap_cands) {
             if (ws->h_counters[CTR_BINFAIL] != 0) __atomic_store_n(&snap->qs_skip, 32u, __ATOMIC_RELAXED);
