@@ -13,6 +13,18 @@
 // counted exactly in a small LDS table (the records are read again -- from LDS) and leave as candidates for k_finish.  No keys, no sort,
 // no bins: HBM sees the line reads and a few bytes of results.
 //
+// The rounds, EIGHT LANES TO A LINE (the unfiltered instantiations): a round is a hash per lane, but a hash's line is fetched ONCE and
+// WHOLE by the eight lanes of its lane's group -- load instruction k of eight: every group reads the line of the hash its lane k holds,
+// lane `sub` words 4 sub .. 4 sub + 3 --, all 64 lines of a wave's round under way at once in 32 registers per lane.  The per-lane walk
+// made about three ACCESSES per hash -- a load instruction touching a distinct line: the head, the 16-byte pieces of the words, the
+// overflow offset -- and the second trip waited for the first; this one makes one, and no trip depends on another.  (The calibration
+// kernels, k_bw_pattern in profiles/r07_kernel_stats.csv, suggest that the chip serves 72 - 76 G accesses per second whatever they carry:
+// a hypothesis -- counted, profiles/r10_tcp_accesses.txt, the per-lane walk made 3.4 accesses per hash at 0.85 of that rate, this one 2.5.)
+// The hash's own lane takes the head from its group's lane 0 and the `ext` offset from lane 7, does the head's arithmetic
+// and the per-hash statistics once; start, words count, inline limit and the second-word mask go back to the group, and every lane
+// classifies its own four words of each line where they landed: every inline word is walked, only lists and words in `ext` are tasks.
+// The filtered form keeps the per-lane walk (a word's column is bookkeeping of its own).
+//
 // Taken by run_batch for snapshots that are ONE packed group and nothing else (the resident index between merges), every column searched,
 // no superseded docs, queries of up to QS_MAX_HASHES hashes with a floor above 2; a query whose records outgrow the LDS array (hot
 // hashes: hundreds of docs per list) fails the batch over to the pipeline above (CTR_BINFAIL), which stays the path for everything else.
@@ -50,8 +62,8 @@ constexpr uint32_t QS_MAX_ROUNDS = 32;             // (a lane remembers which of
 #ifndef FPX_QS_CH
 #define FPX_QS_CH 2
 #endif
-constexpr uint32_t QS_WORDS = FPX_QS_WORDS;                  // words of a hash walked by its lane (four 16-byte pieces of its line); the rare rest by the wave
-constexpr uint32_t QS_CH = FPX_QS_CH;                      // rounds whose line heads are under way together
+constexpr uint32_t QS_WORDS = FPX_QS_WORDS;                  // (FILT) words of a hash walked by its lane (16-byte pieces of its line); the rest are tasks
+constexpr uint32_t QS_CH = FPX_QS_CH;                      // rounds whose hashes a lane holds together ((FILT) whose line heads are under way together)
 constexpr uint32_t QS_TASKS = (((size_t)2u << QS_FLOG2) + ((size_t)8u << QS_TLOG2)) / 8u;      // deferred lists / words of a query (8 bytes each: they live where the filter and the exact table will)
 constexpr uint32_t QS_TASK_WORDS = 8;              // words a deferred "words" task carries at most (a list's task: its header + seven docs)
 constexpr uint32_t QS_TASKS_FILT = QS_TASKS * 8u / 12u;      // (FILT) the same bytes hold fewer tasks: each has a word of its words' columns behind the queue
@@ -137,12 +149,38 @@ __device__ __forceinline__ uint32_t qs_word_cols(uint32_t pm, uint32_t dm, uint3
     return cols;
 }
 
+// ---- eight lanes to a line (the unfiltered rounds): lane l belongs to group l >> 3 and is its lane sub = l & 7.
+// qs_group_bcast<K>: the value of lane K of every group, in all eight of its lanes (a swizzle on the LDS crossbar: and-mask 0x18 keeps the
+// group, or-mask K names the lane; a wave half is 32 lanes, the pattern serves both).  qs_from_sub0<K> / qs_from_sub7<K>: lane K of every
+// group gets the value of the group's lane 0 / lane 7 (a row shift on the DPP crossbar -- a row is two groups --; the other lanes get
+// something they do not look at).  All three want the whole wave active.
+template <uint32_t K> __device__ __forceinline__ uint32_t qs_group_bcast(uint32_t v)
+{
+    return (uint32_t)__builtin_amdgcn_ds_swizzle((int)v, (int)((K << 5) | 0x18u));
+}
+template <uint32_t K> __device__ __forceinline__ uint32_t qs_from_sub0(uint32_t v)
+{
+    if constexpr (K == 0u) return v;
+    else return (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v, 0x110 | (int)K, 0xF, 0xF, true);          // row_shr:K
+}
+template <uint32_t K> __device__ __forceinline__ uint32_t qs_from_sub7(uint32_t v)
+{
+    if constexpr (K == 7u) return v;
+    else return (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v, 0x100 | (int)(7u - K), 0xF, 0xF, true);   // row_shl:7-K
+}
+template <uint32_t K> struct qs_idx { static constexpr uint32_t value = K; };
+template <uint32_t K = 0, class F> __device__ __forceinline__ void qs_for8(F&& f)
+{
+    if constexpr (K < 8u) { f(qs_idx<K>{}); qs_for8<K + 1u>(f); }
+}
+
 // (FPX_QS_PROF: an experiment build -- wave 0 of every workgroup adds the clocks it spent between the kernel's phases to the batch's
 // counters [16 ..], which the host prints; tools/build_variant.sh qs_prof -DFPX_QS_PROF=1)
 #ifdef FPX_QS_PROF
 #define QS_MARK(i) do { if (tid == 0) { const unsigned long long t_ = clock64(); atomicAdd(&qs_cold_args()->a.counters[CTR_HIST + (i)], t_ - t_prev); t_prev = t_; } } while (0)
 // (finer marks inside a phase, slots [6 ..]: QS_SUB0 starts a stretch, QS_SUB(i) adds the clocks since the last of either to slot i; QS_ARRIVED
-// makes every wave wait right there for the loads whose values it names -- the stretch behind it is that wait and nothing else.  The waits
+// makes every wave wait right there for the loads whose values it names -- the stretch behind it is that wait and nothing else.  The
+// unfiltered rounds feed slots 7 and 10 only (a round has no heads-then-words stretch: slots 8 and 9 stay zero).  The waits
 // and the marks' own atomics stretch a query by half: the finer clocks compare builds, they are not shares of the product's time)
 #define QS_SUB0() do { if (tid == 0) t_sub = clock64(); } while (0)
 #define QS_SUB(i) do { if (tid == 0) { const unsigned long long t_ = clock64(); atomicAdd(&qs_cold_args()->a.counters[CTR_HIST + (i)], t_ - t_sub); t_sub = t_; } } while (0)
@@ -217,7 +255,7 @@ __global__ __launch_bounds__(QS_WG) FPX_QS_OCC void k_search_query(QSearchArgs a
     //      The heads of a pair's lines (position bits, double flags) are asked for at the top of its rounds, after dedup, both at once: a
     //      duplicate's line and a hash outside the window are not fetched at all.
     uint32_t hq[2u * QS_CH];
-    uint3 hd[QS_CH];
+    uint3 hd[QS_CH];                                    // (FILT: the per-lane walk's line heads; issue_heads, words_of and probe below are that walk)
     auto line_of = [&](uint32_t h) -> const uint32_t* { return g->lines + (size_t)((h >> HVL) - g->line0) * GROUP_LINE_WORDS; };
     // (the lane's hashes of pair c of a query of n_ hashes at qh_)
     auto load_pair = [&](const uint32_t* qh_, uint32_t n_, uint32_t c, uint32_t& h0, uint32_t& h1) {
@@ -343,7 +381,7 @@ __global__ __launch_bounds__(QS_WG) FPX_QS_OCC void k_search_query(QSearchArgs a
         const uint32_t row = lane >> 4;
         return wbase + (row >= 1u ? r0 : 0u) + (row >= 2u ? r1 : 0u) + (row >= 3u ? r2 : 0u) + (incl - cnt);
     };
-    // (a round reserves its records and its tasks with ONE scan: the two counts side by side in a word -- a wave has at most 64 x 12
+    // (a round reserves its records and its tasks with ONE scan: the two counts side by side in a word -- a wave has at most 64 x 32
     // records and far fewer than 2^16 tasks --, an atomic per counter)
     auto reserve_both = [&](uint32_t cnt, uint32_t nt, uint32_t& tat) -> uint32_t {
         const uint32_t both = cnt | (nt << 16);
@@ -536,8 +574,165 @@ __global__ __launch_bounds__(QS_WG) FPX_QS_OCC void k_search_query(QSearchArgs a
         }
     };
 
+    // ---- the same for a snapshot that searches every column and has no superseded docs (!FILT): EIGHT LANES TO A LINE.  A round is still a
+    //      hash per lane (h; valid: it is a probe), but a hash's line is fetched ONCE and WHOLE, by the eight lanes of its lane's group:
+    //      load instruction k has every group read the line of the hash its lane k holds, lane `sub` words 4 sub .. 4 sub + 3 -- one
+    //      access of the vector-memory front end per line where the per-lane walk made three (head, pieces, offset), and no second trip
+    //      that depends on the first.  All 64 lines of the wave's round are under way at once, 32 registers per lane.
+    //      Then: (1) every lane gets the head (lane 0's first three words) and the `ext` offset (lane 7's last) of ITS OWN hash's line and
+    //      does the head's arithmetic and the per-hash statistics once, as the per-lane walk did; (2) start, words count, inline limit
+    //      and the second-word mask go back to the group, line by line, and every lane classifies its own four words of each line: word
+    //      w = 4 sub + t sits at position p = w - 3 and belongs to the hash iff start <= p < min(start + nwords, inl); (3) ONE
+    //      reservation per wave for the round's records and tasks, the records stored from the lane's 32 registers.  Every inline word
+    //      is walked where it landed: only lists and words in `ext` are tasks.
+    auto round_coop = [&](uint32_t h, bool valid) {
+        const uint32_t sub = lane & 7u;
+        uint32_t L[32];
+        {
+            const uint32_t gv = (uint32_t)(__ballot((int)valid) >> (lane & 56u)) & 0xFFu;          // the group's valid bits
+            qs_for8([&](auto kc) {
+                constexpr uint32_t k = decltype(kc)::value;
+                const uint32_t hk = qs_group_bcast<k>(h);
+                // (a group whose hash is no probe reads the group's first line: one address, no HBM -- no load under a branch)
+                const uint32_t* lp = ((gv >> k) & 1u) != 0u ? line_of(hk) : g->lines;
+                const uint4 v = gload_u4(reinterpret_cast<const uint8_t*>(lp + 4u * sub));
+                L[4 * k] = v.x; L[4 * k + 1] = v.y; L[4 * k + 2] = v.z; L[4 * k + 3] = v.w;
+            });
+        }
+        // (all eight are under way before any is looked at)
+        asm volatile("" : "+v"(L[0]), "+v"(L[1]), "+v"(L[2]), "+v"(L[3]), "+v"(L[4]), "+v"(L[5]), "+v"(L[6]), "+v"(L[7]),
+                          "+v"(L[8]), "+v"(L[9]), "+v"(L[10]), "+v"(L[11]), "+v"(L[12]), "+v"(L[13]), "+v"(L[14]), "+v"(L[15]));
+        asm volatile("" : "+v"(L[16]), "+v"(L[17]), "+v"(L[18]), "+v"(L[19]), "+v"(L[20]), "+v"(L[21]), "+v"(L[22]), "+v"(L[23]),
+                          "+v"(L[24]), "+v"(L[25]), "+v"(L[26]), "+v"(L[27]), "+v"(L[28]), "+v"(L[29]), "+v"(L[30]), "+v"(L[31]));
+        // (1) the lane's own hash: its line is number `sub` of its group
+        uint32_t hx = 0, hy = 0, hz = 0, ov = 0;
+        qs_for8([&](auto kc) {
+            constexpr uint32_t k = decltype(kc)::value;
+            const uint32_t x = qs_from_sub0<k>(L[4 * k]), y = qs_from_sub0<k>(L[4 * k + 1]), z = qs_from_sub0<k>(L[4 * k + 2]), o = qs_from_sub7<k>(L[4 * k + 3]);
+            const bool me = sub == k;
+            hx = me ? x : hx; hy = me ? y : hy; hz = me ? z : hz; ov = me ? o : ov;
+        });
+        const uint64_t bits = valid ? (((uint64_t)hy << 32) | hx) : 0ull;
+        const uint32_t dfl = valid ? hz : 0u;
+        const uint32_t sh = (h & ((1u << HVL) - 1u)) * (uint32_t)NS;
+        const uint32_t pm = (uint32_t)(bits >> sh) & ((1u << NS) - 1u);
+        const uint32_t pos0 = (uint32_t)__popcll(bits & ((1ull << sh) - 1ull));
+        const uint32_t kk = (uint32_t)__popc(pm);
+        const uint32_t dbl_before = pos0 >= 32u ? (uint32_t)__popc(dfl) : (uint32_t)__popc(dfl & ((1u << pos0) - 1u));
+        const uint32_t dm = pos0 >= 32u ? 0u : ((dfl >> pos0) & ((1u << kk) - 1u));
+        const uint32_t nwords = kk + (uint32_t)__popc(dm);
+        const uint32_t n_line = (uint32_t)__popcll(bits) + (uint32_t)__popc(dfl);
+        const uint32_t inl = n_line > GROUP_INLINE ? GROUP_INLINE - 1u : GROUP_INLINE;
+        const uint32_t start = pos0 + dbl_before;
+        // second words of doubles: the t-th double, at position i, has its second word at i + t + 1
+        uint32_t second = 0;
+        for (uint32_t d = dm, t = 0; d != 0u; d &= d - 1u, ++t) second |= 1u << ((uint32_t)__builtin_ctz(d) + t + 1u);
+        // what is per hash is counted here, by its one lane
+        if (valid) { my_probes += nactive; my_reads += 2u; }
+        uint32_t inr = active;
+        if (h < g->lo_all || h > g->hi_all) {          // (rare: see probe)
+            inr = 0u;
+            uint32_t z = 0u;
+            asm volatile("" : "+v"(z));
+#pragma unroll
+            for (uint32_t s = 0; s < NS; ++s) inr |= (h >= s_first[z + s] && h <= s_last[z + s]) ? (1u << s) : 0u;
+        }
+        if (!valid) inr = 0u;
+        my_blocks += (uint32_t)__popc(inr & active & ~pm);         // absent: the reference visits one block, finds nothing and stops
+        // its words behind the line's inline part are in `ext`, at the offset in the line's last word: tasks of up to eight words
+        const uint32_t in_line = min(nwords, start < inl ? inl - start : 0u);
+        const uint32_t in_ext = nwords - in_line;
+        if (in_ext != 0u) my_reads += 2u;
+        const uint32_t chunk = ((h >> GROUP_CHUNK_LOG2) - g->chunk0) & 63u;
+        // (2) every line of the group in turn: start | nwords << 7 | inl << 13 (start <= 96, nwords <= 32, inl <= 29) and the second words
+        uint32_t pa = start | (nwords << 7) | (inl << 13);
+        uint32_t rm32 = 0, sec32 = 0;                    // the lane's words (register 4 k + t) that belong to their line's hash; second words among them
+        const int p0 = (int)(4u * sub) - 3;              // the position of the lane's first word
+        qs_for8([&](auto kc) {
+            constexpr uint32_t k = decltype(kc)::value;
+            const uint32_t ak = qs_group_bcast<k>(pa), bk = qs_group_bcast<k>(second);
+            const int st = (int)(ak & 127u), en = (int)min((ak & 127u) + ((ak >> 7) & 63u), (ak >> 13) & 31u);
+            const int tl = min(max(st - p0, 0), 4), th = min(max(en - p0, 0), 4);
+            const uint32_t rm = ((1u << th) - 1u) & ~((1u << tl) - 1u);
+            const int d = p0 - st;                                            // (<= 28; below -31 the lane has no word of the hash: rm = 0)
+            const uint32_t s4 = (d >= 0 ? bk >> (d & 31) : bk << ((-d) & 31)) & rm;
+            rm32 |= rm << (4u * k); sec32 |= s4 << (4u * k);
+            asm volatile("" : "+v"(pa), "+v"(second), "+v"(rm32), "+v"(sec32));      // (a line after the other: sixteen broadcasts at once cost sixteen registers)
+        });
+        uint32_t neg32 = 0;                                                   // a gap position and a list reference have bit 31
+#pragma unroll
+        for (uint32_t j = 32; j-- != 0u;) neg32 = __builtin_amdgcn_alignbit(neg32, L[j], 31);
+        const uint32_t keep = rm32 & ~neg32;
+        uint32_t cand = rm32 & neg32;                                         // list references and gap positions
+        const uint32_t nrec = (uint32_t)__popc(keep);
+        my_docs += nrec;
+        my_blocks += (uint32_t)__popc(keep & ~sec32);
+        // (the scan histograms: a double is ONE observation of two docs, counted where its second word is -- the upper half of my_probes)
+        if constexpr (SCAN_HIST && (FPX_SH_BITS & 2)) my_probes += (uint32_t)__popc(keep & sec32) << 16;
+        // the lane's register j0 (selects, first of its line's four, then among those: no register array is indexed by a lane's own number)
+        auto word_at = [&](uint32_t j0) -> uint32_t {
+            uint32_t w0 = 0, w1 = 0, w2 = 0, w3 = 0;
+            const uint32_t k0 = j0 >> 2;
+#pragma unroll
+            for (uint32_t k = 0; k < 8u; ++k) {
+                const bool me = k0 == k;
+                w0 = me ? L[4 * k] : w0; w1 = me ? L[4 * k + 1] : w1; w2 = me ? L[4 * k + 2] : w2; w3 = me ? L[4 * k + 3] : w3;
+            }
+            const uint32_t lo = (j0 & 1u) ? w1 : w0, hi = (j0 & 1u) ? w3 : w2;
+            return (j0 & 2u) ? hi : lo;
+        };
+        // a list's task is pushed by the lane that owns the word: its first two lists out of the wave's reservation (le: the address's
+        // word offset in `ext`, lc: the hash's chunk -- its lane's, number j0 >> 2 of the group), a third one by itself
+        // (a gap mark among the lane's words takes one of the two turns without giving a task: a lane with two gaps before a list pushes
+        // that list by itself, through the per-lane atomic -- correct, and how often the headline's data does it is not measured)
+        uint32_t le[2] = {0xFFFFFFFFu, 0xFFFFFFFFu}, lc[2] = {0u, 0u};
+        auto next_list = [&](uint32_t& e, uint32_t& c) {                       // (the whole wave is here)
+            const uint32_t j0 = cand != 0u ? (uint32_t)__builtin_ctz(cand) : 0u;
+            c = (uint32_t)__shfl((int)chunk, (int)((lane & 56u) | (j0 >> 2)));
+            e = cand != 0u ? word_at(j0) : 0xFFFFFFFFu;                        // (0xFFFFFFFF: a gap position, or nothing)
+            cand &= cand - 1u;
+        };
+        if (__ballot((int)(cand != 0u)) != 0ull) {
+            next_list(le[0], lc[0]);
+            if (__ballot((int)(cand != 0u)) != 0ull) next_list(le[1], lc[1]);
+        }
+        const uint32_t nt = (le[0] != 0xFFFFFFFFu ? 1u : 0u) + (le[1] != 0xFFFFFFFFu ? 1u : 0u) + (in_ext + QS_TASK_WORDS - 1u) / QS_TASK_WORDS;
+        // (3)
+        uint32_t tat;
+        emit_at(keep, L, nrec, reserve_both(nrec, nt, tat));
+        if (nt != 0u) {
+            if (tat + nt > TCAP) { s_over_recs = 1u; tat = TCAP; }                // (a full queue: the batch goes the long way)
+            auto put_task = [&](unsigned long long e) { if (tat < TCAP) tasks[tat] = e; ++tat; };
+#pragma unroll
+            for (uint32_t u = 0; u < 2u; ++u)
+                if (le[u] != 0xFFFFFFFFu) put_task(qs_task_list(s_ext[lc[u]] + (le[u] & 0x7FFFFFFFu), lc[u]));
+            if (in_ext != 0u) {
+                const uint32_t* ob = s_ext[chunk] + ov;
+                for (uint32_t j = in_line; j < nwords;) {                      // (start + j >= inl here)
+                    const uint32_t c = min(nwords - j, QS_TASK_WORDS);
+                    put_task(qs_task_words(ob + (start + j - inl), c, second >> j, chunk));
+                    j += c;
+                }
+            }
+        }
+        while (__ballot((int)(cand != 0u)) != 0ull) {                            // (a lane with three lists among its words: hardly ever)
+            uint32_t e, c;
+            next_list(e, c);
+            if (e != 0xFFFFFFFFu) push_task(qs_task_list(s_ext[c] + (e & 0x7FFFFFFFu), c));
+        }
+    };
+
     static_assert(QS_CH == 2, "the rounds run in pairs");
     for (uint32_t c = 0; c < nchunks; ++c) {
+        if constexpr (!FILT) {
+            // a round after the other, each with its 64 lines per wave under way at once (the lane's registers hold one round's)
+            QS_SUB0();
+            QS_ARRIVED2(hq[0], hq[1]);
+            QS_SUB(7);
+            round_coop(hq[0], ((vmask >> (c * QS_CH)) & 1u) != 0u);
+            if (c * QS_CH + 1u < rounds) round_coop(hq[1], ((vmask >> (c * QS_CH + 1u)) & 1u) != 0u);      // (uniform)
+            QS_SUB(10);
+        } else {
         // two rounds at a time, their hashes in hq[0..1]: their line heads, then -- as the heads arrive -- the words of both (and the offset
         // of an overflowing line's rest), then both rounds out of registers
         QS_SUB0();
@@ -558,6 +753,7 @@ __global__ __launch_bounds__(QS_WG) FPX_QS_OCC void k_search_query(QSearchArgs a
         probe(hq[0], hx0, hy0, v0, gw0, ov0);
         if (c * QS_CH + 1u < rounds) probe(hq[1], hx1, hy1, v1, gw1, ov1);              // (uniform)
         QS_SUB(10);
+        }
         // (the window rolls: the next pair moves up, the one after it -- a query of more than 1024 hashes -- sets out)
         hq[0] = hq[2]; hq[1] = hq[3];
         if (c + 2u < nchunks) load_pair(qh, n, c + 2u, hq[2], hq[3]);
