@@ -422,6 +422,7 @@ static const OptInfo OPT_TABLE[OPT_COUNT] = {
     /* OPT_HOT_REFS */           {"hot_refs", "FPX_HOT_REFS", -1, -1, true},                     // 1 | 0 | -1: hot lists reach the score kernel by reference | are copied | by the last batch's records
     /* OPT_QUERY_WG */           {"query_wg", "FPX_QUERY_WG", 1, 0, false},                      // 1 | 0 | 2: a snapshot that is ONE packed group is searched a query per workgroup (fpx_qsearch.hpp) | by the keys - probe - bins - score pipeline | as 1, a group with superseded docs or masked columns too
     /* OPT_SIDE_WG */            {"side_wg", "FPX_SIDE_WG", 0, 0, false},                        // 0 | 1: the file segments next to the group (small decoded, direct-addressed alone) by the pipeline | a query per workgroup (fpx_qside.hpp)
+    /* OPT_HOT_WG */             {"hot_wg", "FPX_HOT_WG", 0, 0, false},                          // 0 | 1: a query whose records outgrow k_search_query's LDS array hands the batch to the pipeline | is redone in doc classes by k_search_classes (fpx_qsearch.hpp; unfiltered only)
 };
 
 int64_t ctx_opt(const Ctx* c, CtxOpt o)

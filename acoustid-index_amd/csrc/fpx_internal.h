@@ -139,6 +139,7 @@ enum Counter : int {
                          // workgroup leaves at its next cancel point, the results are discarded (error.SearchTimeout)
     CTR_TOTAL = 11,      // device-sized path: hit records of the batch (sum of the queries' counts, written by k_l2_scan)
     CTR_BINFAIL = 12,    // k_score_bin: a bin met more distinct (query, doc) pairs than its table takes: the batch is redone on the general path
+    CTR_REDO = 13,       // k_search_query with a redo list (option hot_wg): queries named there for k_search_classes (may exceed the list's capacity)
     CTR_PADS = 15,       // "no record" entries that pad the bins' reservations to whole sectors (BIN_ALIGN): the bins' fill counts include them
     CTR_SLOTCANDS = 14,  // candidates handed from k_score to k_finish through the queries' own slots (statistics)
     CTR_HIST = 16,       // [16..31]: the HIST_SLOTS histogram slots of a launch too small for the spread sets (LEAN_STAT_SETS)
@@ -378,6 +379,7 @@ enum CtxOpt : int {
     OPT_HOT_REFS,
     OPT_QUERY_WG,
     OPT_SIDE_WG,
+    OPT_HOT_WG,
     OPT_COUNT
 };
 constexpr int64_t OPT_UNSET = -2;

@@ -28,6 +28,9 @@
 // Taken by run_batch for snapshots that are ONE packed group and nothing else (the resident index between merges), every column searched,
 // no superseded docs, queries of up to QS_MAX_HASHES hashes with a floor above 2; a query whose records outgrow the LDS array (hot
 // hashes: hundreds of docs per list) fails the batch over to the pipeline above (CTR_BINFAIL), which stays the path for everything else.
+// Option hot_wg = 1 (unfiltered only): such a query is named in the batch's redo list instead, with nothing counted for it, and
+// k_search_classes -- the same body, `CLS` -- walks it once per DOC CLASS, keeping one class of records each time: a doc's postings are
+// all in one class, so each pass counts exactly and the passes' candidates are disjoint.  The batch stays here and nothing backs off.
 // FILT (option query_wg = 2): the same for a group with superseded docs and/or columns outside the snapshot (a live index between a
 // merge and its regroup) -- every word knows its column, as in k_probe_pgroup's per-column walk: a column outside `active` gives no
 // record and no statistic, a doc of a column with a dead set is dropped after it was counted (CTR_DOCS counts before supersession).
@@ -100,6 +103,9 @@ struct QSearchArgs {
     // this counter hands out) -- or null: every gridDim.x-th
     unsigned int* next_q;
     uint32_t stagger;                                          // delays of 3.4 us between the start of a CU's workgroups (0: none)
+    // (option hot_wg = 1, unfiltered) the batch's redo list, or null: a query whose records outgrow the LDS array is named here --
+    // q | its record total << 32, through CTR_REDO -- for k_search_classes instead of failing the batch (redo_cap: entries the list takes)
+    unsigned long long* redo; uint32_t redo_cap;
 };
 
 // The kernel's arguments as its two by-value parameters lay them out in the kernel-argument segment.  Most of them are needed once per
@@ -195,9 +201,18 @@ template <uint32_t K = 0, class F> __device__ __forceinline__ void qs_for8(F&& f
 #endif
 // (MEM: the snapshot has memory segments -- an instantiation of its own: their look-up costs the usual one registers.  FILT: the group has
 // superseded docs and/or columns outside the snapshot -- the supersession filter and the column masks, ga.segs' dead sets)
-template <int NS, bool QS, bool MEM, bool FILT>
-__global__ __launch_bounds__(QS_WG) FPX_QS_OCC void k_search_query(QSearchArgs a, GroupArgs ga)
+// qs_body is both kernels: k_search_query (CLS false) and k_search_classes (CLS true, below) -- a redone query's walk is the same walk,
+// C times, keeping one class of docs each time; what differs sits under `if constexpr (CLS)`.
+constexpr uint32_t QS_MAX_CLASSES = 32;           // doc classes a redone query is searched in at most
+constexpr uint32_t QS_LIST_AHEAD = 8;             // (CLS) loads of 64 docs of a long list that a wave has under way at once
+// a record's doc class: bits of the doc's hash that neither the exact table's slot (h2 & TMASK) nor its pass selector ((h2 >> 16) % passes,
+// passes <= 64) looks at -- and qs_cell takes the doc's own bits, not its hash's --, so a class fills the filter and the table evenly
+__device__ __forceinline__ uint32_t qs_class(uint32_t rec) { return mix32(rec) >> 27; }
+static_assert(QS_MAX_CLASSES == 32u, "qs_class gives five bits");
+template <int NS, bool QS, bool MEM, bool FILT, bool CLS>
+__device__ __forceinline__ void qs_body(const QSearchArgs& a, const GroupArgs& ga)
 {
+    static_assert(!(CLS && FILT), "doc classes: the unfiltered walk only");
 #ifdef FPX_QS_PROF
     unsigned long long t_prev = clock64(), t_sub = 0;
 #endif
@@ -226,12 +241,33 @@ __global__ __launch_bounds__(QS_WG) FPX_QS_OCC void k_search_query(QSearchArgs a
     // What a query's start waits for -- its offsets, then its hashes: two latencies in a row, the second one HBM's -- is asked for while
     // the queries before it are at work: the offsets of the query after the next one as soon as the counter has named it (under this query's
     // counting), the next query's hashes -- the first four rounds' at once -- under this query's tasks and counting.
-    uint32_t q = a.q_begin + blockIdx.x;
+    // (CLS: [q_begin, q_end) are ENTRIES of the redo list -- q | record total << 32 --, a workgroup takes every gridDim.x-th: no queue, no
+    // stagger and nothing asked for a query ahead, this is the rare path)
+    uint32_t ent = a.q_begin + blockIdx.x;
+    uint32_t q = ent, q_recs = 0u;
+    // (CLS) the query's doc classes: the smallest power of two C with (its record total) / C <= QS_REC_CAP / 2 -- the factor of 2 is
+    // room for unequal classes --, known as soon as the entry is read
+    uint32_t ncls = 1u;
+    // (an entry is one word for the whole workgroup, read by a vector load -- the list is written by the kernel before --: named uniform,
+    // so that the query's number, length and classes stay in scalar registers as k_search_query's do)
+    auto take_entry = [&]() {
+        const unsigned long long e = qs_cold_args()->a.redo[ent];
+        q = (uint32_t)__builtin_amdgcn_readfirstlane((int)(uint32_t)e); q_recs = (uint32_t)__builtin_amdgcn_readfirstlane((int)(uint32_t)(e >> 32));
+        ncls = 1u;
+        while ((unsigned long long)ncls * (QS_REC_CAP / 2u) < (unsigned long long)q_recs) ncls *= 2u;
+    };
+    if constexpr (CLS) take_entry();
+    (void)q_recs;
     uint32_t qn = q + gridDim.x;                        // the query after this one ...
     uint32_t n, nn = 0u;
     uint64_t nq_lo = 0;                                 // ... and where its hashes are (nn of them)
     const uint32_t* qh;
-    {
+    if constexpr (CLS) {
+        const uint64_t q_lo = a.offsets[q];
+        n = (uint32_t)(a.offsets[q + 1] - q_lo);
+        qh = a.hashes_base + q_lo;
+        qn = 0xFFFFFFFFu;
+    } else {
         const uint64_t q_lo = a.offsets[q];
         n = (uint32_t)(a.offsets[q + 1] - q_lo);
         qh = a.hashes_base + q_lo;
@@ -292,9 +328,17 @@ __global__ __launch_bounds__(QS_WG) FPX_QS_OCC void k_search_query(QSearchArgs a
   // they end together and the next kernel starts in lockstep again (0.412 -> 0.43 ms per batch, and jittery).  So the host asks for both -- the
   // counter and the delays -- only for a batch that finds the device to itself (run_batch: Ctx::qs_running).
   // Only where a workgroup has four or more queries ahead of it: a small batch is one query's latency.
-  if (const uint32_t stagger = qs_cold_args()->a.stagger; stagger != 0u && a.q_end - a.q_begin >= 4u * gridDim.x)
+  if (const uint32_t stagger = qs_cold_args()->a.stagger; !CLS && stagger != 0u && a.q_end - a.q_begin >= 4u * gridDim.x)
       for (uint32_t i = 0; i < ((blockIdx.x >> 8) & 3u) * stagger; ++i) __builtin_amdgcn_s_sleep(127);
   for (;;) {
+    if constexpr (CLS) {
+        // (uniform, before the query's first barrier) more classes than a query gets: the batch goes the long way.  The workgroup's other
+        // entries are left undone with it -- the host hands the whole batch to the pipeline on CTR_BINFAIL
+        if (ncls > QS_MAX_CLASSES) {
+            if (tid == 0) atomicMax(&qs_cold_args()->a.counters[CTR_BINFAIL], 1ull);
+            return;
+        }
+    }
     const uint32_t rounds = (n + QS_WG - 1u) / QS_WG, nchunks = (rounds + QS_CH - 1u) / QS_CH;
     // the query's hash set: 2^sbits >= 2 n slots
     uint32_t sbits = 8u;
@@ -356,6 +400,28 @@ __global__ __launch_bounds__(QS_WG) FPX_QS_OCC void k_search_query(QSearchArgs a
     __syncthreads();                                    // (the set is done with: its slots are the record array now)
     QS_MARK(1);
 
+    // ---- (CLS) pass `cls` of the query's ncls classes walks the query again and keeps the records of that class only: a doc's postings
+    //      are all in one class, so a pass's counts are exact and the passes' candidates are disjoint.  The hash set above is built once.
+    const uint32_t cmask = ncls - 1u;
+    (void)cmask;
+    const bool has_next = qn < a.q_end;                      // (uniform; CLS: never -- qn names no query)
+    // (what the tail learns about the query after the next one, for the hand-over behind the passes)
+    uint32_t q2 = 0u;
+    bool has_q2 = false;
+    uint64_t o2_lo = 0;
+    uint32_t o2_hi = 0u;                                    // (the low word of its end: a query is shorter than 2^32 hashes)
+  for (uint32_t cls = 0; cls < ncls; ++cls) {
+    if constexpr (CLS) {
+        if (cls != 0u) {
+            __syncthreads();                            // (the pass before has read its records, its table and its flags)
+            if (tid == 0) { s_count = 0u; s_ntask = 0u; }
+            load_pair(qh, n, 0u, hq[0], hq[1]);         // (the rounds' first pair again: the pass before left its last one there)
+            __syncthreads();
+        }
+    }
+    // (a record of this pass: every emission site asks -- the rounds' words, the tasks' words and lists, the wave-walked lists, the memory table)
+    auto in_class = [&](uint32_t rec) -> bool { return (qs_class(rec) & cmask) == cls; };
+    (void)in_class;
     const uint32_t active = g->active, nactive = (uint32_t)__popc(active);
     uint32_t my_blocks = 0, my_docs = 0, my_probes = 0, my_reads = 0;
     // (FILT) a doc of column s that a newer segment supersedes (src/common.zig:158; the column's dead set, k_probe_pgroup's test)
@@ -419,6 +485,7 @@ __global__ __launch_bounds__(QS_WG) FPX_QS_OCC void k_search_query(QSearchArgs a
     };
     // (one record of some lanes of the wave: the wave's turns, long lists)
     auto emit1 = [&](bool kp, uint32_t doc) {
+        if constexpr (CLS) kp = kp && in_class(doc);
         const unsigned long long m = __ballot((int)kp);
         if (m == 0ull) return;
         uint32_t base = 0;
@@ -604,6 +671,16 @@ __global__ __launch_bounds__(QS_WG) FPX_QS_OCC void k_search_query(QSearchArgs a
                           "+v"(L[8]), "+v"(L[9]), "+v"(L[10]), "+v"(L[11]), "+v"(L[12]), "+v"(L[13]), "+v"(L[14]), "+v"(L[15]));
         asm volatile("" : "+v"(L[16]), "+v"(L[17]), "+v"(L[18]), "+v"(L[19]), "+v"(L[20]), "+v"(L[21]), "+v"(L[22]), "+v"(L[23]),
                           "+v"(L[24]), "+v"(L[25]), "+v"(L[26]), "+v"(L[27]), "+v"(L[28]), "+v"(L[29]), "+v"(L[30]), "+v"(L[31]));
+        // (CLS) which of the lane's 32 words, read as docs, are of this pass's class: asked here, word by word, while little else is
+        // live (thirty-two hashes side by side cost the registers the rounds do not have)
+        uint32_t cm32 = CLS ? 0u : 0xFFFFFFFFu;
+        if constexpr (CLS) {
+#pragma unroll
+            for (uint32_t j = 32u; j-- != 0u;) {
+                cm32 = (cm32 << 1) | (in_class(L[j]) ? 1u : 0u);     // (from the last word down, a bit at a time: a mask per word would be a register per word)
+                asm volatile("" : "+v"(cm32), "+v"(L[j]));
+            }
+        }
         // (1) the lane's own hash: its line is number `sub` of its group
         uint32_t hx = 0, hy = 0, hz = 0, ov = 0;
         qs_for8([&](auto kc) {
@@ -664,9 +741,12 @@ __global__ __launch_bounds__(QS_WG) FPX_QS_OCC void k_search_query(QSearchArgs a
         for (uint32_t j = 32; j-- != 0u;) neg32 = __builtin_amdgcn_alignbit(neg32, L[j], 31);
         const uint32_t keep = rm32 & ~neg32;
         uint32_t cand = rm32 & neg32;                                         // list references and gap positions
-        const uint32_t nrec = (uint32_t)__popc(keep);
+        uint32_t nrec = (uint32_t)__popc(keep);
         my_docs += nrec;
         my_blocks += (uint32_t)__popc(keep & ~sec32);
+        // (CLS) what the walk SAW is counted above, whatever the class; the records are this pass's class only
+        const uint32_t kept = keep & cm32;
+        if constexpr (CLS) nrec = (uint32_t)__popc(kept);
         // (the scan histograms: a double is ONE observation of two docs, counted where its second word is -- the upper half of my_probes)
         if constexpr (SCAN_HIST && (FPX_SH_BITS & 2)) my_probes += (uint32_t)__popc(keep & sec32) << 16;
         // the lane's register j0 (selects, first of its line's four, then among those: no register array is indexed by a lane's own number)
@@ -699,7 +779,7 @@ __global__ __launch_bounds__(QS_WG) FPX_QS_OCC void k_search_query(QSearchArgs a
         const uint32_t nt = (le[0] != 0xFFFFFFFFu ? 1u : 0u) + (le[1] != 0xFFFFFFFFu ? 1u : 0u) + (in_ext + QS_TASK_WORDS - 1u) / QS_TASK_WORDS;
         // (3)
         uint32_t tat;
-        emit_at(keep, L, nrec, reserve_both(nrec, nt, tat));
+        emit_at(kept, L, nrec, reserve_both(nrec, nt, tat));
         if (nt != 0u) {
             if (tat + nt > TCAP) { s_over_recs = 1u; tat = TCAP; }                // (a full queue: the batch goes the long way)
             auto put_task = [&](unsigned long long e) { if (tat < TCAP) tasks[tat] = e; ++tat; };
@@ -755,8 +835,12 @@ __global__ __launch_bounds__(QS_WG) FPX_QS_OCC void k_search_query(QSearchArgs a
         QS_SUB(10);
         }
         // (the window rolls: the next pair moves up, the one after it -- a query of more than 1024 hashes -- sets out)
-        hq[0] = hq[2]; hq[1] = hq[3];
-        if (c + 2u < nchunks) load_pair(qh, n, c + 2u, hq[2], hq[3]);
+        // ((CLS) no window: the next pair is asked for when this one is done -- two registers the class masks need, on the rare path)
+        if constexpr (CLS) { if (c + 1u < nchunks) load_pair(qh, n, c + 1u, hq[0], hq[1]); }
+        else {
+            hq[0] = hq[2]; hq[1] = hq[3];
+            if (c + 2u < nchunks) load_pair(qh, n, c + 2u, hq[2], hq[3]);
+        }
     }
     // ---- MemorySegment.search (src/MemorySegment.zig:44-54) for all memory segments at once: the query's probes looked up in the snapshot's
     //      table of their live postings -- a bit per 256 hash values says "nothing there" for nine probes in ten --, four rounds' loads out
@@ -778,7 +862,7 @@ __global__ __launch_bounds__(QS_WG) FPX_QS_OCC void k_search_query(QSearchArgs a
                 for (uint32_t i = blo[u]; i < bhi[u]; ++i) {                       // (a bucket holds a posting or two)
                     const uint64_t it = gload_u64(a.mem_tab + i);
                     if ((uint32_t)(it >> 32) > mh[u]) break;
-                    if ((uint32_t)(it >> 32) == mh[u]) {
+                    if ((uint32_t)(it >> 32) == mh[u] && (!CLS || in_class((uint32_t)it - gmin))) {
                         const uint32_t at = atomicAdd(&s_count, 1u);
                         if (at < QS_REC_CAP) recs[at] = (uint32_t)it - gmin; else s_over_recs = 1u;      // (a memory segment's doc may lie below gmin: modulo 2^32)
                     }
@@ -792,7 +876,6 @@ __global__ __launch_bounds__(QS_WG) FPX_QS_OCC void k_search_query(QSearchArgs a
     // (... and the query after THAT is asked of the launch's counter: the answer has the tasks to arrive in)
     uint32_t r2 = 0u;
     if (tid == 0u) { unsigned int* const next_q = qs_cold_args()->a.next_q; if (next_q != nullptr) r2 = atomicAdd(next_q, 1u); }
-    const bool has_next = qn < a.q_end;                      // (uniform)
     QS_SUB0();
     QS_ARRIVED2(nn, (uint32_t)nq_lo); QS_SUB(11);
     // (this query's floor, which the exact pass will want: every lane asks for the one word -- a vector load stays in flight
@@ -873,6 +956,12 @@ __global__ __launch_bounds__(QS_WG) FPX_QS_OCC void k_search_query(QSearchArgs a
                         if (dead_in(s, gmin + doc)) km &= ~(1u << j0);
                     }
                 }
+                if constexpr (CLS) {                    // (counted above, whatever the class)
+                    uint32_t cm = 0u;
+#pragma unroll
+                    for (uint32_t j = QS_TASK_WORDS; j-- != 0u;) cm = (cm << 1) | (in_class(d[j]) ? 1u : 0u);
+                    km &= cm;
+                }
                 emit(km, d);
                 while (lm != 0u) {                      // (a list inside the words: the next pass's)
                     const uint32_t j0 = (uint32_t)__builtin_ctz(lm);
@@ -891,6 +980,19 @@ __global__ __launch_bounds__(QS_WG) FPX_QS_OCC void k_search_query(QSearchArgs a
                     const uint32_t* list = reinterpret_cast<const uint32_t*>(((uint64_t)__shfl((uint32_t)((uint64_t)p >> 32), src) << 32) | __shfl((uint32_t)(uint64_t)p, src));
                     const uint32_t eff_s = __shfl(eff, src), T_s = __shfl(Tl, src), from = __shfl(xin, src);
                     const uint32_t col_s = FILT ? (uint32_t)__shfl(lcol, src) : 0u;
+                    if constexpr (CLS) {
+                        // (a redone query IS its long lists -- a hot hash is a list of 1000 docs in every column -- and a wave walks them one
+                        // after the other, a trip to memory per 64 docs.  Here QS_LIST_AHEAD x 64 docs are asked for before the first is
+                        // looked at: a step of 8192 queries, 8 of them with 32 such lists each, 3.92 -> 3.17 ms, profiles/r11_hot_wg.txt)
+                        for (uint32_t o2 = from; o2 < eff_s; o2 += 64u * QS_LIST_AHEAD) {
+                            uint32_t dv[QS_LIST_AHEAD];
+#pragma unroll
+                            for (uint32_t u = 0; u < QS_LIST_AHEAD; ++u)
+                                dv[u] = o2 + 64u * u + lane < eff_s ? gload_u32(list + 1u + T_s + o2 + 64u * u + lane) : 0u;
+#pragma unroll
+                            for (uint32_t u = 0; u < QS_LIST_AHEAD; ++u) emit1(o2 + 64u * u + lane < eff_s, dv[u]);
+                        }
+                    } else
                     for (uint32_t o2 = from; o2 < eff_s; o2 += 64u) {
                         bool kp = o2 + lane < eff_s;
                         const uint32_t dv = kp ? gload_u32(list + 1u + T_s + o2 + lane) : 0u;
@@ -918,7 +1020,7 @@ __global__ __launch_bounds__(QS_WG) FPX_QS_OCC void k_search_query(QSearchArgs a
         const uint32_t w_doubles = (uint32_t)wave_total(my_probes >> 16);
         // (the counter's answer -- the query after the next one -- goes to the workgroup behind the barrier below)
         if (tid == 0u) s_q2 = qs_cold_args()->a.next_q != nullptr ? a.q_begin + 2u * gridDim.x + r2 : qn + gridDim.x;
-        if (lane == 0u) {
+        if (lane == 0u && (!CLS || cls == 0u)) {           // (CLS: every pass sees the same blocks and docs; the first one reports them)
             if (w_doubles) atomicAdd(&wg_h[0], w_doubles);
             if (w_reads) atomicAdd(&wg_reads, w_reads);
             if (w_blocks) atomicAdd(&wg_blocks, w_blocks);
@@ -930,10 +1032,8 @@ __global__ __launch_bounds__(QS_WG) FPX_QS_OCC void k_search_query(QSearchArgs a
     QS_MARK(3);
     // ---- the offsets of the query after the next one set out as soon as it is known, and the next query's cancel flag: they travel under
     //      this query's counting (vector loads of one address, as the floor's above)
-    const uint32_t q2 = (uint32_t)__builtin_amdgcn_readfirstlane((int)s_q2);
-    const bool has_q2 = has_next && q2 < a.q_end;           // (uniform)
-    uint64_t o2_lo = 0;
-    uint32_t o2_hi = 0u;                                    // (the low word of its end: a query is shorter than 2^32 hashes)
+    q2 = (uint32_t)__builtin_amdgcn_readfirstlane((int)s_q2);
+    has_q2 = has_next && q2 < a.q_end;                      // (uniform)
     if (has_q2) {
         uint32_t qv = q2;
         asm volatile("" : "+v"(qv));
@@ -953,19 +1053,34 @@ __global__ __launch_bounds__(QS_WG) FPX_QS_OCC void k_search_query(QSearchArgs a
         }
     }
     const qs_kargs_t kt = qs_cold_args();               // (the tail's arguments: read here, once per query)
-    if (tid == 0) {
+    // (s_over_recs and the counts are final: the barrier above.)  A query whose records outgrew the array, where the batch has a redo list
+    // (option hot_wg, unfiltered): it is named there with its record total -- s_count went on counting past the array's end -- and gives
+    // NO statistic and no candidate here: k_search_classes redoes it and owns them all.  A query whose TASK QUEUE overflowed has no total
+    // (the tasks beyond the queue were never read) and would overflow the same queue in every class: that one fails the batch as before.
+    const bool q_stats = !CLS || cls == 0u;                  // (CLS: blocks, docs, probes, reads and the histograms in one pass only)
+    bool q_redo = false;
+    if constexpr (!FILT && !CLS) {
+        if (s_over_recs != 0u || s_count > QS_REC_CAP) q_redo = kt->a.redo != nullptr && s_ntask <= TCAP;
+    }
+    if (tid == 0 && q_redo) {
+        const unsigned long long at = atomicAdd(&kt->a.counters[CTR_REDO], 1ull);
+        if (at < (unsigned long long)kt->a.redo_cap) kt->a.redo[at] = (unsigned long long)q | ((unsigned long long)s_count << 32);
+    }
+    if (tid == 0 && !q_redo) {
         unsigned long long* st = kt->a.stat_sets + (size_t)(q % LEAN_STAT_SETS) * 8u;
-        if (wg_reads) atomicAdd(&st[4], wg_reads);
-        if (wg_blocks) atomicAdd(&st[1], wg_blocks);
-        const uint32_t block_size = kt->ga.g.block_size;
-        if (wg_blocks && block_size != 512u) atomicAdd(&st[5], wg_blocks * (unsigned long long)block_size - wg_blocks * 512ull);
-        if (wg_docs) atomicAdd(&st[2], wg_docs);
-        if (wg_probes) atomicAdd(&st[3], wg_probes);
-        if (s_count) atomicAdd(&st[7], (unsigned long long)s_count);                  // the query's hit records
-        if constexpr (QS) { unsigned long long* const qstats = kt->a.qstats; if (qstats) qstats[q] = wg_blocks | (wg_docs << 32); }
+        if (q_stats) {
+            if (wg_reads) atomicAdd(&st[4], wg_reads);
+            if (wg_blocks) atomicAdd(&st[1], wg_blocks);
+            const uint32_t block_size = kt->ga.g.block_size;
+            if (wg_blocks && block_size != 512u) atomicAdd(&st[5], wg_blocks * (unsigned long long)block_size - wg_blocks * 512ull);
+            if (wg_docs) atomicAdd(&st[2], wg_docs);
+            if (wg_probes) atomicAdd(&st[3], wg_probes);
+        }
+        if (s_count) atomicAdd(&st[7], (unsigned long long)s_count);                  // the query's hit records ((CLS) this class's: summed over the passes)
+        if constexpr (QS) { if (q_stats) { unsigned long long* const qstats = kt->a.qstats; if (qstats) qstats[q] = wg_blocks | (wg_docs << 32); } }
         if (s_over_recs || s_count > QS_REC_CAP) atomicMax(&kt->a.counters[CTR_BINFAIL], 1ull);
     }
-    if (tid < HIST_SLOTS - 1u) {                             // (slot 15: hist_observe's sink)
+    if (tid < HIST_SLOTS - 1u && q_stats && !q_redo) {       // (slot 15: hist_observe's sink)
         const unsigned long long v = tid == HIST_COUNT ? wg_probes : tid == HIST_DOCS ? wg_docs : tid == HIST_BLOCKS ? wg_blocks : (unsigned long long)wg_h[tid];
         if (v != 0ull) atomicAdd(&kt->a.stat_sets[(size_t)LEAN_STAT_SETS * 8u + (size_t)(q % LEAN_STAT_SETS) * HIST_SLOTS + tid], v);
     }
@@ -974,7 +1089,7 @@ __global__ __launch_bounds__(QS_WG) FPX_QS_OCC void k_search_query(QSearchArgs a
     const uint32_t floor_q = (uint32_t)__builtin_amdgcn_readfirstlane((int)floor_v);
     const uint32_t sb = kt->a.sb;
     const uint64_t smax = sb >= 32u ? 0xFFFFFFFFull : ((1ull << sb) - 1ull);
-    if (s_over_recs == 0u && nrec != 0u && nrec >= floor_q) {
+    if (s_over_recs == 0u && !q_redo && nrec != 0u && nrec >= floor_q) {
         uint32_t passes = 1u;
         for (uint32_t pass = 0; pass < passes; ++pass) {
             if (pass != 0u) {
@@ -1041,6 +1156,7 @@ __global__ __launch_bounds__(QS_WG) FPX_QS_OCC void k_search_query(QSearchArgs a
             }
         }
     }
+  }   // (the classes: one pass unless CLS.  The candidates of all of them are in the buffer and the shared list: s_ccnt was not reset)
     // ---- hand-over: up to QCAND_SLOTS candidates stay in the query's own slots, more move to the shared list entirely
     __syncthreads();
     QS_MARK(4);
@@ -1064,15 +1180,42 @@ __global__ __launch_bounds__(QS_WG) FPX_QS_OCC void k_search_query(QSearchArgs a
         }
     }
     QS_MARK(5);
-    if (!has_next) break;
-    q = qn; n = nn; qh = a.hashes_base + nq_lo;
-    qn = q2; nn = 0u; nq_lo = 0;
-    if (has_q2) {
-        nq_lo = ((uint64_t)(uint32_t)__builtin_amdgcn_readfirstlane((int)(uint32_t)(o2_lo >> 32)) << 32) | (uint32_t)__builtin_amdgcn_readfirstlane((int)(uint32_t)o2_lo);
-        nn = (uint32_t)__builtin_amdgcn_readfirstlane((int)(o2_hi - (uint32_t)o2_lo));
+    if constexpr (CLS) {                                // the workgroup's next entry of the redo list
+        ent += gridDim.x;
+        if (ent >= a.q_end) break;
+        take_entry();
+        const uint64_t q_lo = a.offsets[q];
+        n = (uint32_t)(a.offsets[q + 1] - q_lo);
+        qh = a.hashes_base + q_lo;
+        load_pair(qh, n, 0u, hq[0], hq[1]);
+        load_pair(qh, n, 1u, hq[2], hq[3]);
+        ask_cancel();
+    } else {
+        if (!has_next) break;
+        q = qn; n = nn; qh = a.hashes_base + nq_lo;
+        qn = q2; nn = 0u; nq_lo = 0;
+        if (has_q2) {
+            nq_lo = ((uint64_t)(uint32_t)__builtin_amdgcn_readfirstlane((int)(uint32_t)(o2_lo >> 32)) << 32) | (uint32_t)__builtin_amdgcn_readfirstlane((int)(uint32_t)o2_lo);
+            nn = (uint32_t)__builtin_amdgcn_readfirstlane((int)(o2_hi - (uint32_t)o2_lo));
+        }
     }
     __syncthreads();                                    // (the candidate buffer and the flags have been read: the next query may reset them)
   }
+}
+
+template <int NS, bool QS, bool MEM, bool FILT>
+__global__ __launch_bounds__(QS_WG) FPX_QS_OCC void k_search_query(QSearchArgs a, GroupArgs ga)
+{
+    qs_body<NS, QS, MEM, FILT, false>(a, ga);
+}
+
+// k_search_classes: the queries that k_search_query named in the batch's redo list (option hot_wg = 1; a.q_begin .. a.q_end are entries of
+// that list), each searched once per doc class.  The same two by-value parameters: qs_cold_args()'s layout holds for both kernels.
+// The rare path: a query's walk C times over (its lines are in the L2 after the first), four workgroups per CU not asked for.
+template <int NS, bool MEM>
+__global__ __launch_bounds__(QS_WG) FPX_QS_OCC void k_search_classes(QSearchArgs a, GroupArgs ga)
+{
+    qs_body<NS, true, MEM, false, true>(a, ga);
 }
 
 // zeroes what a batch of k_search_query adds to: the batch's counters and the statistics sets (one launch instead of two memsets)

@@ -181,6 +181,10 @@ static void launch_probe_group(bool packed, bool ns8, bool binned, bool qs, dim3
 constexpr int FPX_SPLIT = 1;   // internal: candidate key does not fit 64 bits, split the batch
 constexpr int FPX_REDO_QS = 3; // internal: the one-workgroup-per-query path gave up (a query's records outgrew its LDS array, scores too wide): the pipeline
 constexpr int FPX_REDO = 2;    // internal: the device-sized path met something only the general path handles (a full bin, ...)
+// (option hot_wg) queries of a batch of B that k_search_classes redoes in doc classes; a batch with more of them goes to the pipeline.
+// A policy guess, not a measurement: an eighth of the batch, and a handful for a small one.
+constexpr uint32_t QS_REDO_MIN = 4, QS_REDO_SHARE = 8;
+constexpr uint32_t qs_redo_limit(uint32_t B) { return B / QS_REDO_SHARE > QS_REDO_MIN ? B / QS_REDO_SHARE : QS_REDO_MIN; }
 
 static unsigned bits_for(uint64_t n)   // number of bits needed to represent values in [0, n)
 {
@@ -655,7 +659,10 @@ static int run_batch(Snapshot* snap, Workspace* ws, const QueryBatch* resident, 
     if (qs_path) {
         const GroupDesc& gd = snap->h_group[0];
         const Group* grp = snap->groups[0].get();
-        if ((rc = grow(&ws->d_qcand, &ws->cap_qcand, (size_t)B * QCAND_SLOTS + 2 * ((size_t)B / 2 + 1)))) return rc;
+        // (option hot_wg = 1, unfiltered: the batch's redo list -- B entries, behind the slots and their counts)
+        const bool hot_wg = !qs_filt && ctx_opt(snap->ctx, OPT_HOT_WG) == 1;
+        const size_t qcand_words = (size_t)B * QCAND_SLOTS + 2 * ((size_t)B / 2 + 1);
+        if ((rc = grow(&ws->d_qcand, &ws->cap_qcand, qcand_words + (hot_wg ? (size_t)B : 0)))) return rc;
         uint64_t* d_qcand = ws->d_qcand;
         uint32_t* d_qcand_n = reinterpret_cast<uint32_t*>(ws->d_qcand + (size_t)B * QCAND_SLOTS);
         const size_t cand_guess0 = std::max<size_t>(1u << 16, (size_t)B * 64);
@@ -675,6 +682,7 @@ static int run_batch(Snapshot* snap, Workspace* ws, const QueryBatch* resident, 
         qa.counters = ws->d_counters; qa.stat_sets = reinterpret_cast<unsigned long long*>(ws->d_def_count + def_stat_off);
         qa.qstats = want_q ? ws->d_qstats : nullptr; qa.cancel = cancel;
         if (snap->n_mem != 0 && snap->mem_items != 0) { qa.mem_tab = snap->d_memtab; qa.mem_bucket = snap->d_membucket; qa.mem_bits = snap->d_membits; }
+        if (hot_wg) { qa.redo = reinterpret_cast<unsigned long long*>(ws->d_qcand + qcand_words); qa.redo_cap = B; }
         const GroupArgs gargs{gd, snap->d_direct};
         // as many workgroups as the chip holds at once (LDS: QS_WGS_PER_CU per CU); each takes every gridDim.x-th query
         static std::atomic<int> cus_of[64];
@@ -720,14 +728,17 @@ static int run_batch(Snapshot* snap, Workspace* ws, const QueryBatch* resident, 
         hipLaunchKernelGGL(k_finish, dim3((B + 127) / 128), dim3(128), 0, st,
                            (const uint64_t*)ws->d_cands[0], (uint64_t)0, d_opts, B, sbf, partial ? 1 : 0, d_res, out_cap, d_res_n,
                            (const uint64_t*)d_qcand, (const uint32_t*)d_qcand_n, stats ? ws->d_counters : nullptr);
-        {
+        // (the batch's counters and statistics sets into the host's mapped copies: after the first pass, and again after a redo)
+        auto publish = [&]() -> int {
             PublishArgs pa{};
             pa.counters = ws->d_counters; pa.h_counters = mapped_address(ws->h_counters);
             pa.a_src = ws->d_def_count; pa.a_dst = mapped_address(ws->h_def_count); pa.a_n = (uint32_t)def_words;
             if (!pa.h_counters || !pa.a_dst) { set_error("page-locked host memory is not mapped into the device"); return FPX_E_DEVICE; }
             hipLaunchKernelGGL(k_publish, dim3(4), dim3(256), 0, st, pa);
             FPX_HIP(hipGetLastError());
-        }
+            return FPX_OK;
+        };
+        if ((rc = publish())) return rc;
         FPX_HIP(hipEventRecord(ws->ev_end, st));
         FPX_SYNC(ws);
 #ifdef FPX_QS_PROF
@@ -742,14 +753,41 @@ static int run_batch(Snapshot* snap, Workspace* ws, const QueryBatch* resident, 
             if (ws->h_counters[CTR_BINFAIL] != 0) __atomic_store_n(&snap->qs_skip, 32u, __ATOMIC_RELAXED);
             return FPX_REDO_QS;
         }
+        // ---- option hot_wg: the queries whose records outgrew the LDS array were named in the redo list, with nothing counted and no
+        //      candidate; k_search_classes searches each of them once per doc class (fpx_qsearch.hpp), into the same slots and shared list.
+        //      A few of them: the batch stays here and nothing backs off.  More than qs_redo_limit(B): the pipeline and the back-off, as
+        //      before -- a walk per class costs more than the pipeline's one once much of a batch is hot, and hot traffic comes in runs.
+        //      (The shared list's length is known to the host only behind a synchronisation of its own: the sort below needs it.)
+        const uint64_t R = hot_wg ? ws->h_counters[CTR_REDO] : 0;
+        if (R != 0) {
+            if (R > qs_redo_limit(B) || R > qa.redo_cap) {
+                __atomic_store_n(&snap->qs_skip, 32u, __ATOMIC_RELAXED);
+                return FPX_REDO_QS;
+            }
+            qa.q_begin = 0u; qa.q_end = (uint32_t)R; qa.next_q = nullptr; qa.stagger = 0u;      // (entries of the list; all pieces of a chunked upload have arrived)
+            const dim3 rgrid(std::min<uint32_t>((uint32_t)R, (uint32_t)cus * QS_WGS_PER_CU));
+            auto launch = [&](auto kernel) { hipLaunchKernelGGL(kernel, rgrid, dim3(QS_WG), QS_LDS_BYTES, st, qa, gargs); };
+            if (grp->ns == 8u) { if (qa.mem_tab != nullptr) launch(k_search_classes<8, true>); else launch(k_search_classes<8, false>); }
+            else { if (qa.mem_tab != nullptr) launch(k_search_classes<16, true>); else launch(k_search_classes<16, false>); }
+            if ((rc = publish())) return rc;
+            FPX_HIP(hipEventRecord(ws->ev_end, st));
+            FPX_SYNC(ws);
+            if (ws->h_counters[CTR_BINFAIL] != 0 || ws->h_counters[CTR_MAXSCORE] != 0 || ws->h_counters[CTR_CANDS] > ws->cap_cands) {
+                if (ws->h_counters[CTR_BINFAIL] != 0) __atomic_store_n(&snap->qs_skip, 32u, __ATOMIC_RELAXED);
+                return FPX_REDO_QS;
+            }
+        }
         uint64_t Cf = 0;
         int ccur2 = 0;
-        if (ws->h_counters[CTR_CANDS] != 0) {
-            // some queries have more candidates than slots: sort the shared list and finish again (second round trip)
+        if (ws->h_counters[CTR_CANDS] != 0 || R != 0) {
+            // some queries have more candidates than slots: sort the shared list and finish again (second round trip); the same
+            // second k_finish takes the redone queries' candidates from their slots
             Cf = ws->h_counters[CTR_CANDS];
-            const size_t tb2 = sort_u64_temp_bytes(Cf, 0, 64);
-            if ((rc = grow(reinterpret_cast<uint8_t**>(&ws->d_temp), &ws->cap_temp, tb2 + 256))) return rc;
-            FPX_HIP(sort_u64(ws->d_temp, ws->cap_temp, ws->d_cands[0], ws->d_cands[1], Cf, 0, 64, st, &ccur2));
+            if (Cf != 0) {
+                const size_t tb2 = sort_u64_temp_bytes(Cf, 0, 64);
+                if ((rc = grow(reinterpret_cast<uint8_t**>(&ws->d_temp), &ws->cap_temp, tb2 + 256))) return rc;
+                FPX_HIP(sort_u64(ws->d_temp, ws->cap_temp, ws->d_cands[0], ws->d_cands[1], Cf, 0, 64, st, &ccur2));
+            }
             if (stats) FPX_HIP(hipMemsetAsync(&ws->d_counters[CTR_SLOTCANDS], 0, sizeof(unsigned long long), st));
             hipLaunchKernelGGL(k_finish, dim3((B + 127) / 128), dim3(128), 0, st,
                                (const uint64_t*)ws->d_cands[ccur2], Cf, d_opts, B, sbf, partial ? 1 : 0, d_res, out_cap, d_res_n,
@@ -777,7 +815,7 @@ static int run_batch(Snapshot* snap, Workspace* ws, const QueryBatch* resident, 
             stats->probe_kernel_ms += ms; stats->total_gpu_ms += total_ms; stats->probe_launches += 1;
             stats->probe_kernel_bytes += blocks * 512ull + bytes_off;
             stats->probe_kernel_fetched_bytes += (dreads + 1) / 2 * 128ull;
-            stats->path_flags |= 1u | (Cf ? 2u : 0u) | 4u | 64u | (qs_filt ? 256u : 0u);
+            stats->path_flags |= 1u | (Cf ? 2u : 0u) | 4u | 64u | (qs_filt ? 256u : 0u) | (R != 0 ? 1024u : 0u);
         }
         if ((rc = deliver_qstats())) return rc;
         ws->hint_P = P; ws->hint_H = std::max<uint64_t>(records, 1);          // (sizes the pipeline's bins should a later batch take it)

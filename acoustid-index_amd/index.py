@@ -56,7 +56,9 @@ class Context:
         option's smallest (-1, or -2 for 'group_packed' / 'bin_q_log2') puts it back to the environment / default.  'query_wg': 1 | 0 | 2
         -- a snapshot that is one packed group searched a query per workgroup | by the pipeline | as 1, a group with superseded docs or
         masked columns too (Stats.path_flags bit 8).  'side_wg': 0 | 1 -- the file segments next to the group (small decoded, direct-addressed
-        alone) searched by the pipeline | a query per workgroup (Stats.path_flags bit 9)"""
+        alone) searched by the pipeline | a query per workgroup (Stats.path_flags bit 9).  'hot_wg': 0 | 1 -- a query whose hit records
+        outgrow the query-per-workgroup kernel's array hands the batch to the pipeline | is redone in doc classes, the batch staying on
+        that path (Stats.path_flags bit 10)"""
         check(lib().fpx_ctx_set_option(self.h, name.encode(), int(value)))
 
     def trim(self):

@@ -87,7 +87,9 @@ typedef struct {
                                    bit 8: the batch (or its part 0) ran the FILTERED k_search_query: a packed group with superseded
                                    docs and/or columns outside the snapshot, searched a query per workgroup ("query_wg" 2),
                                    bit 9: the batch (or its part 1) ran k_search_side: the file segments next to the group -- small decoded
-                                   ones, direct-addressed ones on their own -- searched a query per workgroup ("side_wg" 1) */
+                                   ones, direct-addressed ones on their own -- searched a query per workgroup ("side_wg" 1),
+                                   bit 10: some queries of the batch (or of its part 0) were redone in doc classes by k_search_classes:
+                                   their hit records outgrew k_search_query's array, the batch stayed on that path ("hot_wg" 1) */
     uint64_t probe_kernel_fetched_bytes; /* block bytes the main probe kernel really fetched, in 128-byte lines: a probe
                                    whose hash the segment's presence bits know to be absent counts as a visited block (as in
                                    the reference) without the block being read, and a block that is read costs two lines up
@@ -124,6 +126,13 @@ int  fpx_ctx_device(const fpx_ctx *ctx);     /* the HIP ordinal the context live
  *                        batches of queries k_search_query would take (up to 4096 hashes, a floor above 2); a query whose records
  *                        outgrow the workgroup's array hands that snapshot or part back to the pipeline -- and the next 32 batches of
  *                        that snapshot (or part) stay on the pipeline without trying, bit 9 clear: hot-hash traffic comes in runs
+ *   "hot_wg"             0 | 1   a query whose hit records outgrow k_search_query's array of 8192 (hot hashes: a dozen of 1000+ docs)
+ *                        hands the whole batch to the pipeline and keeps the next 32 batches there (default 0) | is named in a redo
+ *                        list and searched again by k_search_classes, once per DOC CLASS -- 2 .. 32 classes, sized by its record
+ *                        count --, the rest of the batch staying where it is and nothing backing off (csrc/fpx_qsearch.hpp;
+ *                        fpx_stats.path_flags bit 10).  Unfiltered snapshots only ("query_wg" 2's filtered form keeps the hand-back);
+ *                        a batch with more such queries than max(4, B / 8), or a query that needs more than 32 classes, is
+ *                        handed back as under 0
  *   "fast"               1 | 0   the device-sized path (one host round trip per batch; default 1)
  *   "binned"             1 | 0   groups drop their records into bins of a few queries, scored a bin per workgroup (default 1)
  *   "rec32"              1 | 0   4-byte records in the bins where the doc ids leave room (default 1)
