@@ -7,10 +7,11 @@
 //   MemorySegment.search    src/MemorySegment.zig:44-54
 //   SearchResults.incr/finish src/common.zig:121-171  + Segments.hasNewerCommit src/Index.zig:133-149
 //
-// GPU formulation (a batch of B queries at once) -- two of them, chosen per batch by run_batch:
+// GPU formulation (a batch of B queries at once) -- two of them, chosen per batch by run_batch, which fills a Batch and calls one driver:
 //   A. a snapshot that is ONE packed group (the resident index between merges): k_search_query (fpx_qsearch.hpp), a QUERY PER WORKGROUP --
-//      dedup, the group's lines, counting and the floor in one kernel, the hit records never leaving the CU -- then k_finish, k_publish.
-//   B. everything else, the pipeline over all the batch's hashes:
+//      dedup, the group's lines, counting and the floor in one kernel, the hit records never leaving the CU -- then k_finish, k_publish
+//      (run_query_wg; run_side_wg for the file segments next to the group).
+//   B. everything else, the pipeline over all the batch's hashes (make_keys, launch_probes; run_device_sized, run_single or run_general):
 //      1. k_make_keys*     (hash, q) keys, packed hash << QB | q; ordered by hash bucket (fpx_keyorder.hpp / fpx_sort.hip) or per query in LDS:
 //                          duplicates become adjacent (dedupSorted) and neighbouring probes walk neighbouring lines
 //      2. probe kernels    by storage form -- blocks: k_probe (fpx_probe_generic.hpp), k_probe_lean8 (fpx_probe_lean.hpp), k_probe_small;
@@ -151,36 +152,35 @@ static int grow_pair(uint64_t* p[2], size_t* cap, size_t need)
     return FPX_OK;
 }
 
+// n keys of pair[0] sorted on their bits [lo, hi), with the workspace's temporary storage; *cur: which of the pair holds them afterwards
+static int sort_keys(Workspace* ws, uint64_t* pair[2], uint64_t n, unsigned lo, unsigned hi, hipStream_t st, int* cur)
+{
+    const size_t tb = sort_u64_temp_bytes(n, lo, hi);
+    if (const int rc = grow(reinterpret_cast<uint8_t**>(&ws->d_temp), &ws->cap_temp, tb + 256)) return rc;
+    FPX_HIP(sort_u64(ws->d_temp, ws->cap_temp, pair[0], pair[1], n, lo, hi, st, cur));
+    return FPX_OK;
+}
+
 // k_probe_group's instantiations: columns of a directory line (8 | 16), records binned in the flush, per-query scan statistics
 static void launch_probe_group(bool packed, bool ns8, bool binned, bool qs, dim3 grid, hipStream_t st, const ProbeArgs& a, const GroupArgs& g)
 {
     const size_t dyn = (size_t)FSTAGE_CAP * sizeof(uint64_t) + (binned ? (size_t)FSTAGE_CAP * sizeof(uint16_t) : 0u);       // stage (+ ranks)
-    if (packed) {                                 // a dense group: its words live in its lines (fpx_pgroup.hpp; + the prefetched line heads)
-#define FPX_LPP(NS, BN, QSV) hipLaunchKernelGGL((k_probe_pgroup<NS, BN, QSV>), grid, dim3(FK_WG), (size_t)FSTAGE_CAP * sizeof(uint64_t) + PK_HEAD_LDS, st, a, g)
-        if (ns8) {
-            if (binned) { if (qs) FPX_LPP(8, true, true); else FPX_LPP(8, true, false); }
-            else { if (qs) FPX_LPP(8, false, true); else FPX_LPP(8, false, false); }
-        } else {
-            if (binned) { if (qs) FPX_LPP(16, true, true); else FPX_LPP(16, true, false); }
-            else { if (qs) FPX_LPP(16, false, true); else FPX_LPP(16, false, false); }
-        }
-#undef FPX_LPP
-        return;
-    }
-#define FPX_LPG(NS, BN, QSV) hipLaunchKernelGGL((k_probe_group<NS, BN, QSV>), grid, dim3(FK_WG), dyn, st, a, g)
-    if (ns8) {
-        if (binned) { if (qs) FPX_LPG(8, true, true); else FPX_LPG(8, true, false); }
-        else { if (qs) FPX_LPG(8, false, true); else FPX_LPG(8, false, false); }
-    } else {
-        if (binned) { if (qs) FPX_LPG(16, true, true); else FPX_LPG(16, true, false); }
-        else { if (qs) FPX_LPG(16, false, true); else FPX_LPG(16, false, false); }
-    }
-#undef FPX_LPG
+    const size_t dyn_packed = (size_t)FSTAGE_CAP * sizeof(uint64_t) + PK_HEAD_LDS;      // (+ the prefetched line heads)
+#define FPX_LP(K, LDS, NS, BN, QSV) hipLaunchKernelGGL((K<NS, BN, QSV>), grid, dim3(FK_WG), LDS, st, a, g)
+#define FPX_LP_QS(K, LDS, NS, BN) do { if (qs) FPX_LP(K, LDS, NS, BN, true); else FPX_LP(K, LDS, NS, BN, false); } while (0)
+#define FPX_LP_BN(K, LDS, NS) do { if (binned) FPX_LP_QS(K, LDS, NS, true); else FPX_LP_QS(K, LDS, NS, false); } while (0)
+#define FPX_LP_NS(K, LDS) do { if (ns8) FPX_LP_BN(K, LDS, 8); else FPX_LP_BN(K, LDS, 16); } while (0)
+    if (packed) FPX_LP_NS(k_probe_pgroup, dyn_packed);      // a dense group: its words live in its lines (fpx_pgroup.hpp)
+    else FPX_LP_NS(k_probe_group, dyn);
+#undef FPX_LP_NS
+#undef FPX_LP_BN
+#undef FPX_LP_QS
+#undef FPX_LP
 }
 
 constexpr int FPX_SPLIT = 1;   // internal: candidate key does not fit 64 bits, split the batch
 constexpr int FPX_REDO_QS = 3; // internal: the one-workgroup-per-query path gave up (a query's records outgrew its LDS array, scores too wide): the pipeline
-constexpr int FPX_REDO = 2;    // internal: the device-sized path met something only the general path handles (a full bin, ...)
+constexpr int FPX_REDO = 2;    // internal: the device-sized or the single-query path met something only the general path handles (a full bin, ...)
 // (option hot_wg) queries of a batch of B that k_search_classes redoes in doc classes; a batch with more of them goes to the pipeline.
 // A policy guess, not a measurement: an eighth of the batch, and a handful for a small one.
 constexpr uint32_t QS_REDO_MIN = 4, QS_REDO_SHARE = 8;
@@ -212,14 +212,22 @@ static int ensure_queries(Workspace* ws, size_t B)
     return FPX_OK;
 }
 
+// a query's effective floor -- src/MultiIndex.zig:304: the default floor uses the RAW query length (before dedup)
+static uint32_t query_floor(const fpx_opts& o, uint64_t raw_len) { return o.has_min_score ? o.min_score : (uint32_t)((raw_len + 19) / 20); }
+static uint32_t min_floor(const uint64_t* offsets, const fpx_opts* opts, uint32_t B)
+{
+    uint32_t lo = 0xFFFFFFFFu;
+    for (uint32_t q = 0; q < B; ++q) lo = std::min(lo, query_floor(opts[q], offsets[q + 1] - offsets[q]));
+    return lo;
+}
+
 static void fill_opts(std::vector<uint32_t>& h_opts, const fpx_opts* opts, const uint64_t* offsets, uint32_t B)
 {
     h_opts.resize((size_t)B * 4);
     for (uint32_t q = 0; q < B; ++q) {
         const uint64_t raw_len = offsets[q + 1] - offsets[q];
         h_opts[q * 4 + 0] = opts[q].max_results;
-        // src/MultiIndex.zig:304: the default floor uses the RAW query length (before dedup)
-        h_opts[q * 4 + 1] = opts[q].has_min_score ? opts[q].min_score : (uint32_t)((raw_len + 19) / 20);
+        h_opts[q * 4 + 1] = query_floor(opts[q], raw_len);
         h_opts[q * 4 + 2] = opts[q].min_score_pct;
         h_opts[q * 4 + 3] = (uint32_t)raw_len;
     }
@@ -255,6 +263,7 @@ static int sync_deadline(Workspace* ws, double t_start, uint32_t timeout_ms)
     return FPX_OK;
 }
 #define FPX_SYNC(ws) do { const int _rc = sync_deadline((ws), t_start, timeout_ms); if (_rc != FPX_OK) return _rc; } while (0)
+#define FPX_SYNC_BATCH(b) do { const int _rc = sync_deadline((b).ws, (b).t_start, (b).timeout_ms); if (_rc != FPX_OK) return _rc; } while (0)
 
 // The count table of the batch's key order (fpx_keyorder.hpp): `bits` hash bits below the `win_bits` a hash window fixes, fewer
 // when the table would outgrow KO_MAX_CELLS.  Layout of ws->d_kocnt: [B x nb counts | nb totals | pad | the key count (u64)].
@@ -314,37 +323,33 @@ template <typename T> static T* mapped_address(T* host)
 // waited for, hand the bytes to the caller.  Beyond a megabyte the host's second copy costs more than the driver's slow
 // path saves (2.6 MB at batch 8192: +0.08 ms): those go directly, after the wait.
 constexpr size_t STAGED_OUT_MAX = (size_t)1 << 20;
+static int ensure_h_out(Workspace* ws, size_t bytes)
+{
+    if (bytes <= ws->cap_h_out) return FPX_OK;
+    if (ws->h_out) (void)hipHostFree(ws->h_out);
+    ws->h_out = nullptr; ws->cap_h_out = 0;
+    const size_t ncap = bytes * 5 / 4 + 4096;
+    FPX_HIP(hipHostMalloc(reinterpret_cast<void**>(&ws->h_out), ncap, hipHostMallocMapped));
+    ws->cap_h_out = ncap;
+    return FPX_OK;
+}
 static int stage_results(Workspace* ws, uint32_t B, uint32_t out_cap, hipStream_t st, bool* staged)
 {
     const size_t bytes = (size_t)B * sizeof(uint32_t) + (size_t)B * out_cap * sizeof(fpx_result);
     *staged = bytes <= STAGED_OUT_MAX;
     if (!*staged) return FPX_OK;
-    if (bytes > ws->cap_h_out) {
-        if (ws->h_out) (void)hipHostFree(ws->h_out);
-        ws->h_out = nullptr; ws->cap_h_out = 0;
-        const size_t ncap = bytes * 5 / 4 + 4096;
-        FPX_HIP(hipHostMalloc(reinterpret_cast<void**>(&ws->h_out), ncap, hipHostMallocMapped));
-        ws->cap_h_out = ncap;
-    }
+    if (const int rc = ensure_h_out(ws, bytes)) return rc;
     FPX_HIP(hipMemcpyAsync(ws->h_out, ws->d_out_n, (size_t)B * sizeof(uint32_t), hipMemcpyDeviceToHost, st));
     if (out_cap) FPX_HIP(hipMemcpyAsync(ws->h_out + (size_t)B * sizeof(uint32_t), ws->d_out, (size_t)B * out_cap * sizeof(fpx_result), hipMemcpyDeviceToHost, st));
     return FPX_OK;
 }
 // the same staging, filled by k_finish itself: where it writes a batch's counts and results (mapped addresses of h_out)
-static int staged_targets(Workspace* ws, const Ctx* ctx, uint32_t B, uint32_t out_cap, bool* staged, uint32_t** d_n, fpx_result** d_res)
+static int staged_targets(Workspace* ws, uint32_t B, uint32_t out_cap, bool* staged, uint32_t** d_n, fpx_result** d_res)
 {
     const size_t bytes = (size_t)B * sizeof(uint32_t) + (size_t)B * out_cap * sizeof(fpx_result);
-    const int64_t staged_opt = -1;                   // (the built-in STAGED_OUT_MAX)
-    const size_t staged_max = staged_opt < 0 ? STAGED_OUT_MAX : (size_t)staged_opt;
-    *staged = bytes <= staged_max;
+    *staged = bytes <= STAGED_OUT_MAX;
     if (!*staged) return FPX_OK;
-    if (bytes > ws->cap_h_out) {
-        if (ws->h_out) (void)hipHostFree(ws->h_out);
-        ws->h_out = nullptr; ws->cap_h_out = 0;
-        const size_t ncap = bytes * 5 / 4 + 4096;
-        FPX_HIP(hipHostMalloc(reinterpret_cast<void**>(&ws->h_out), ncap, hipHostMallocMapped));
-        ws->cap_h_out = ncap;
-    }
+    if (const int rc = ensure_h_out(ws, bytes)) return rc;
     uint8_t* d = mapped_address(ws->h_out);
     if (!d) { *staged = false; return FPX_OK; }
     *d_n = reinterpret_cast<uint32_t*>(d);
@@ -415,156 +420,239 @@ void ctx_hist_add(Ctx* c, const uint64_t* slots, uint64_t unbucketed)
     if (unbucketed) c->scan_hist[HIST_SLOTS].fetch_add(unbucketed, std::memory_order_relaxed);
 }
 
-static int run_batch(Snapshot* snap, Workspace* ws, const QueryBatch* resident, uint32_t q0,
-                     const uint32_t* hashes, const uint64_t* offsets, uint32_t B,
-                     const fpx_opts* opts, uint32_t timeout_ms, bool partial,
-                     fpx_result* out, uint32_t out_cap, uint32_t* out_n, fpx_stats* stats, const Exchange* ex = nullptr,
-                     bool no_fast = false, double t_call = 0.0, uint64_t* q_blocks = nullptr, uint64_t* q_docs = nullptr, bool no_qs = false)
+// which paths an entry of run_batch may take: run_with_redos walks down this list as a path hands the batch back
+enum class Try { First, NoQueryWg, GeneralOnly };
+
+// One entry of run_batch: what every path reads.  run_batch fills it once and passes it by reference -- a plain bag of values.
+struct Batch {
+    Snapshot* snap; Workspace* ws; hipStream_t st;
+    const QueryBatch* resident; uint32_t q0;                                    // a batch resident in HBM, and the view's first query in it
+    uint32_t B; uint64_t P, base; unsigned qb;                                  // queries, their hashes, the first one's absolute position, bits of q
+    const uint32_t* hashes; const uint64_t* offsets; const fpx_opts* opts;      // the caller's host arrays
+    const uint32_t* d_hashes_base; const uint64_t* d_offsets; const uint32_t* d_opts;      // ... and where the kernels read them
+    bool staged_single;                                                         // one small query, read from mapped host memory: its positions start at 0
+    const uint32_t* cancel; double t_start; uint32_t timeout_ms;
+    bool partial; fpx_result* out; uint32_t out_cap; uint32_t* out_n; fpx_stats* stats;
+    bool want_q; uint64_t* q_blocks; uint64_t* q_docs;                          // per-query scan statistics, when the caller asked for them
+    size_t def_cap, def_stat_off, def_words;                                    // the deferred lists' layout (ws->d_def_count)
+    uint32_t up_chunks, up_q[Workspace::UP_CHUNKS + 1];                         // a chunked upload: the pieces' query ranges
+};
+
+// ---- steps that several paths share --------------------------------------------------------------------------------------------
+// the kernels' statistics, LEAN_STAT_SETS copies of 8 slots on separate cache lines (a workgroup adds to set blockIdx.x % LEAN_STAT_SETS), summed
+struct StatSums { unsigned long long reads = 0, blocks = 0, docs = 0, probes = 0, dreads = 0, bytes_off = 0, pads = 0, records = 0; };
+static StatSums sum_stat_sets(const unsigned long long* ls)
 {
-    const bool probe_only = ex && ex->mode == 1, score_only = ex && ex->mode == 2;
-    // the deadline counts from the API call's entry (one deadline per search, src/MultiIndex.zig:314-322), however often the
-    // batch re-enters here (a redo on the general path, the two halves of a split)
-    const double t_start = t_call != 0.0 ? t_call : now_ms();
-    hipStream_t st = ws->stream;
-    std::memset(ws->batch_hist, 0, sizeof ws->batch_hist);
-    __atomic_store_n(ws->h_cancel, 0u, __ATOMIC_RELEASE);           // (the stream is idle: the previous call synchronised it)
-    const uint32_t* cancel = timeout_ms ? ws->d_cancel : nullptr;
-    const uint64_t base = offsets[0];
-    const uint64_t P = offsets[B] - base;
-    const unsigned qb = bits_for(B);            // q in [0, B)
-    unsigned sb = 1;                            // bits of the score field; sized after scoring
-
-    // ---- the batch: resident in HBM already, or uploaded from the caller's host buffers
-    int rc;
-    if ((rc = ensure_queries(ws, B))) return rc;       // d_out_n (+ staging for non-resident batches)
-    if ((rc = grow_pair(ws->d_keys, &ws->cap_keys, (size_t)P + 1))) return rc;
-    if (!partial && (rc = grow(&ws->d_out, &ws->cap_out, (size_t)B * out_cap + 1))) return rc;
-    static_assert(sizeof(fpx_result) == 8, "fpx_result layout");
-    const uint32_t* d_hashes_base;
-    const uint64_t* d_offsets;
-    const uint32_t* d_opts;
-    bool staged_single = false;
-    // A single /_search (B == 1) is latency bound and every HIP call costs microseconds (and a runtime lock shared with
-    // the other host threads): its pipeline runs with fixed sizes, reads its inputs from and writes its outputs to
-    // device-mapped pinned memory (no copy, memset or event calls), synchronises once, and is checked at the end;
-    // anything that does not fit falls back to the general path.
-    bool single_fast = B == 1 && !partial && !ex && !no_fast && P != 0 && out_cap <= SINGLE_OUT_MAX &&
-                       (snap->n_lean == 0 || P * snap->n_file < lean_min_probes(snap->ctx));
-    // ---- ONE WORKGROUP PER QUERY (fpx_qsearch.hpp): the snapshot is one packed group and nothing else, every column of it searched, no
-    //      superseded docs -- the resident index between merges --, the queries short enough for their hash set and their floor above the
-    //      legacy protocol's: dedup, probe, count and floor happen in ONE kernel, no keys are made or ordered, no record reaches HBM.
-    //      Anything else, and a batch that kernel hands back (hot hashes: a query's records outgrow its LDS array), runs the pipeline below.
-    //      Option query_wg 2: a group with superseded docs or columns outside the snapshot too, by the kernel's filtered instantiation (qs_filt).
-    bool qs_path = false, qs_filt = false;
-    const int64_t query_wg = ctx_opt(snap->ctx, OPT_QUERY_WG);
-    if (!ex && !no_fast && !no_qs && !single_fast && B >= 2u && P != 0 && qb <= 24u && snap->n_file == 0 && snap->n_solo == 0 && snap->n_group == 1 &&
-        snap->n_direct != 0 && (snap->n_mem == 0 || snap->mem_items == 0 || snap->d_memtab != nullptr) && snap->groups[0]->packed && query_wg != 0) {
-        const GroupDesc& gd = snap->h_group[0];
-        qs_filt = gd.any_dead != 0u || gd.active != (gd.nseg >= 32u ? 0xFFFFFFFFu : ((1u << gd.nseg) - 1u));
-        qs_path = !qs_filt || query_wg == 2;
-        for (uint32_t q = 0; q < B && qs_path; ++q) {
-            const uint64_t raw_len = offsets[q + 1] - offsets[q];
-            qs_path = raw_len <= QS_MAX_HASHES && (opts[q].has_min_score ? opts[q].min_score : (uint32_t)((raw_len + 19) / 20)) > 2u;
-        }
-        if (qs_path) {
-            // (after a batch that was handed back: the next ones do not try again at once -- hot-hash traffic comes in runs)
-            uint32_t skip = __atomic_load_n(&snap->qs_skip, __ATOMIC_RELAXED);
-            if (skip != 0u) { __atomic_store_n(&snap->qs_skip, skip - 1u, __ATOMIC_RELAXED); qs_path = false; }
-        }
+    StatSums s;
+    for (uint32_t i = 0; i < LEAN_STAT_SETS; ++i) {
+        s.reads += ls[i * 8 + 0]; s.blocks += ls[i * 8 + 1]; s.docs += ls[i * 8 + 2]; s.probes += ls[i * 8 + 3]; s.dreads += ls[i * 8 + 4];
+        s.bytes_off += ls[i * 8 + 5];            // (block sizes other than 512 in the direct-addressed forms: the difference, mod 2^64)
+        s.pads += ls[i * 8 + 6]; s.records += ls[i * 8 + 7];
     }
-
-    // ---- ... and the same for the file segments NEXT TO the group (fpx_qside.hpp; option side_wg = 1): a snapshot -- part 1 of a live one, or a
-    //      whole young index -- of small decoded and direct-addressed-alone segments only, none of them a hash-window slice, no group, no
-    //      memory-segment postings.  The queries' rule is parts_take's, so a batch in two parts never splits between paths by query.
-    bool side_path = false;
-    if (!qs_path && !ex && !no_fast && !no_qs && !single_fast && B >= 2u && P != 0 && qb <= 24u && ctx_opt(snap->ctx, OPT_SIDE_WG) == 1 &&
-        snap->n_group == 0 && snap->n_lean == 0 && snap->n_gen == 0 && snap->n_file == snap->n_small && snap->n_direct == snap->n_solo &&
-        snap->n_small + snap->n_solo != 0 && (snap->n_mem == 0 || snap->mem_items == 0)) {
-        side_path = true;
-        for (const SegDesc& d : snap->h_file) side_path = side_path && d.own_flags == 0u && d.items && d.sbucket && d.sfirst && d.scode;
-        for (const SegDesc& d : snap->h_direct) side_path = side_path && d.own_flags == 0u && d.drec && d.primary;
-        for (uint32_t q = 0; q < B && side_path; ++q) {
-            const uint64_t raw_len = offsets[q + 1] - offsets[q];
-            side_path = raw_len <= QS_MAX_HASHES && (opts[q].has_min_score ? opts[q].min_score : (uint32_t)((raw_len + 19) / 20)) > 2u;
-        }
-        if (side_path) {
-            // (the back-off after a hand-back, as above: this snapshot's own count -- a part 1 is a snapshot of its own)
-            uint32_t skip = __atomic_load_n(&snap->qs_skip, __ATOMIC_RELAXED);
-            if (skip != 0u) { __atomic_store_n(&snap->qs_skip, skip - 1u, __ATOMIC_RELAXED); side_path = false; }
-        }
+    return s;
+}
+static const unsigned long long* host_stat_sets(const Batch& b) { return reinterpret_cast<const unsigned long long*>(b.ws->h_def_count + b.def_stat_off); }
+static unsigned long long* device_stat_sets(const Batch& b) { return reinterpret_cast<unsigned long long*>(b.ws->d_def_count + b.def_stat_off); }
+// block bytes the probe kernels fetched, where they kept no spread statistics (k_probe_direct / k_probe_group: 64-byte units)
+static unsigned long long unspread_fetched_bytes(const Workspace* ws, const Snapshot* snap)
+{
+    return snap->n_direct ? ws->h_counters[CTR_LEAN_READS] * 64ull + (snap->n_file ? ws->h_counters[CTR_BYTES] : 0ull) : ws->h_counters[CTR_BYTES];
+}
+// compute units of the context's device: asked of the runtime once per device
+static int device_cus(const Ctx* ctx)
+{
+    static std::atomic<int> cus_of[64];
+    int cus = cus_of[(unsigned)ctx->device & 63u].load(std::memory_order_relaxed);
+    if (cus == 0) {
+        if (hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, ctx->device) != hipSuccess || cus <= 0) { (void)hipGetLastError(); cus = 256; }
+        cus_of[(unsigned)ctx->device & 63u].store(cus, std::memory_order_relaxed);
     }
+    return cus;
+}
+// per-query candidate slots: [B][QCAND_SLOTS] keys, then [B] counts, then the list of heavy queries [B], then `extra_words` of the caller's
+// (`extra`); and the shared list the queries with more candidates than slots write to, at its first guess
+struct CandSlots { uint64_t* qcand = nullptr; uint32_t* qcand_n = nullptr; uint32_t* heavy = nullptr; uint64_t* extra = nullptr; };
+static int ensure_cand_slots(Workspace* ws, uint32_t B, size_t extra_words, CandSlots* cs)
+{
+    const size_t words = (size_t)B * QCAND_SLOTS + 2 * ((size_t)B / 2 + 1);
+    if (const int rc = grow(&ws->d_qcand, &ws->cap_qcand, words + extra_words)) return rc;
+    cs->qcand = ws->d_qcand;
+    cs->qcand_n = reinterpret_cast<uint32_t*>(ws->d_qcand + (size_t)B * QCAND_SLOTS);
+    cs->heavy = reinterpret_cast<uint32_t*>(ws->d_qcand + (size_t)B * QCAND_SLOTS + (size_t)B / 2 + 1);
+    cs->extra = ws->d_qcand + words;
+    const size_t cand_guess0 = std::max<size_t>(1u << 16, (size_t)B * 64);
+    return ws->cap_cands < cand_guess0 ? grow_pair(ws->d_cands, &ws->cap_cands, cand_guess0) : FPX_OK;
+}
+// where k_finish writes: the caller's device table (`partial`), the workspace's, or -- a small batch -- the pinned staging itself
+struct ResultsTo { fpx_result* res; uint32_t* n; bool staged; };
+static int results_target(Batch& b, ResultsTo* to)
+{
+    to->res = b.partial ? b.out : b.ws->d_out;
+    to->n = b.partial ? b.out_n : b.ws->d_out_n;
+    to->staged = false;
+    return b.partial ? FPX_OK : staged_targets(b.ws, b.B, b.out_cap, &to->staged, &to->n, &to->res);
+}
+// k_finish over the batch: `cands[C]` the sorted shared list, the queries' own slots next to it; count_slots: it adds the slots' candidates up
+static void launch_finish(Batch& b, const uint64_t* cands, uint64_t C, uint32_t sb, const CandSlots& cs, fpx_result* d_res, uint32_t* d_res_n, bool count_slots)
+{
+    hipLaunchKernelGGL(k_finish, dim3((b.B + 127) / 128), dim3(128), 0, b.st,
+                       cands, C, b.d_opts, b.B, sb, b.partial ? 1 : 0, d_res, b.out_cap, d_res_n,
+                       (const uint64_t*)cs.qcand, (const uint32_t*)cs.qcand_n, count_slots ? b.ws->d_counters : nullptr);
+}
+// some queries have more candidates than slots: sort the shared list's Cf entries and finish again (second round trip)
+static int finish_crowded(Batch& b, uint32_t sb, const CandSlots& cs, const ResultsTo& to, uint64_t Cf)
+{
+    Workspace* ws = b.ws; int rc, ccur = 0;
+    if (Cf != 0 && (rc = sort_keys(ws, ws->d_cands, Cf, 0, 64, b.st, &ccur))) return rc;
+    if (b.stats) FPX_HIP(hipMemsetAsync(&ws->d_counters[CTR_SLOTCANDS], 0, sizeof(unsigned long long), b.st));
+    launch_finish(b, ws->d_cands[ccur], Cf, sb, cs, to.res, to.n, b.stats != nullptr);
+    FPX_HIP(hipGetLastError());
+    FPX_HIP(hipMemcpyAsync(&ws->h_counters[CTR_SLOTCANDS], &ws->d_counters[CTR_SLOTCANDS], sizeof(unsigned long long), hipMemcpyDeviceToHost, b.st));
+    FPX_HIP(hipEventRecord(ws->ev_end, b.st));
+    FPX_SYNC_BATCH(b);
+    return FPX_OK;
+}
+// the batch's counters, and with `stat_sets` the deferred lists' counts and the statistics sets, into the host's mapped copies; b_src: the bins' counts too
+constexpr size_t BINQ_HEAD = 64 / sizeof(uint32_t);                          // room for the BinArgs the kernels read
+static int publish(Batch& b, bool stat_sets, const uint32_t* b_src = nullptr, uint32_t b_n = 0, uint32_t b_stride = 0)
+{
+    Workspace* ws = b.ws;
+    PublishArgs pa{};
+    pa.counters = ws->d_counters; pa.h_counters = mapped_address(ws->h_counters);
+    pa.a_src = ws->d_def_count; pa.a_dst = stat_sets ? mapped_address(ws->h_def_count) : nullptr; pa.a_n = stat_sets ? (uint32_t)b.def_words : 0u;
+    uint32_t* d_hbins = b_src ? mapped_address(ws->h_bins) : nullptr;
+    if (b_src) { pa.b_src = b_src; pa.b_dst = d_hbins + BINQ_HEAD; pa.b_n = b_n; pa.b_stride = b_stride; }
+    if (!pa.h_counters || (stat_sets && !pa.a_dst) || (b_src && !d_hbins)) { set_error("page-locked host memory is not mapped into the device"); return FPX_E_DEVICE; }
+    hipLaunchKernelGGL(k_publish, dim3(4), dim3(256), 0, b.st, pa);
+    FPX_HIP(hipGetLastError());
+    return FPX_OK;
+}
+// did a query-per-workgroup kernel hand the batch back?  (a full LDS array: the snapshot's next batches do not try again at once)
+static bool handed_back(const Workspace* ws, Snapshot* snap)
+{
+    if (ws->h_counters[CTR_BINFAIL] == 0 && ws->h_counters[CTR_MAXSCORE] == 0 && ws->h_counters[CTR_CANDS] <= ws->cap_cands) return false;
+    if (ws->h_counters[CTR_BINFAIL] != 0) __atomic_store_n(&snap->qs_skip, 32u, __ATOMIC_RELAXED);
+    return true;
+}
+static int deliver_qstats(Batch& b)
+{
+    if (!b.want_q) return FPX_OK;
+    std::vector<unsigned long long> hq(b.B);
+    FPX_HIP(hipMemcpy(hq.data(), b.ws->d_qstats, (size_t)b.B * sizeof(unsigned long long), hipMemcpyDeviceToHost));
+    for (uint32_t q = 0; q < b.B; ++q) {
+        if (b.q_blocks) b.q_blocks[q] = hq[q] & 0xFFFFFFFFull;
+        if (b.q_docs) b.q_docs[q] = hq[q] >> 32;
+    }
+    return FPX_OK;
+}
+// k_score's filter and table: a counting filter sized for ~2x the average number of records per query (8 KB .. 64 KB of LDS) + a 16 KB
+// exact table.  The filter only has to keep cells that collect < min_score records below the floor: with the usual floor (n / 20 = 50 for
+// 1 k-hash queries) a cell may hold several docs' records and still reject them, so a quarter of the size does; the LDS saved more than
+// doubles the resident workgroups (k_score is occupancy bound).  With a floor of 1 or 2 (the legacy protocol) nearly every record passes
+// it: the LDS goes to a larger exact table instead, so that the count needs 2 passes rather than 6.
+static void score_filter_sizes(uint32_t floor_min, uint64_t H, uint32_t B, uint32_t* log2f_out, uint32_t* log2t_out)
+{
+    uint32_t log2f = 11;
+    while (log2f < 14 && (1ull << log2f) < 2 * (H / B + 1)) ++log2f;
+    log2f = std::max(11u, log2f - (floor_min >= 8u ? 2u : floor_min >= 3u ? 1u : 0u));
+    uint32_t log2t = SCORE_TABLE_LOG2;
+    if (floor_min <= 2u && H / B > (1u << SCORE_TABLE_LOG2)) { log2t = 13; log2f = 11; }
+    static const hipError_t lds_attrs[3] = {
+        hipFuncSetAttribute(reinterpret_cast<const void*>(&k_score<32, false>), hipFuncAttributeMaxDynamicSharedMemorySize, 128 * 1024),
+        hipFuncSetAttribute(reinterpret_cast<const void*>(&k_score<8, false>), hipFuncAttributeMaxDynamicSharedMemorySize, 128 * 1024),
+        hipFuncSetAttribute(reinterpret_cast<const void*>(&k_score<32, true>), hipFuncAttributeMaxDynamicSharedMemorySize, 128 * 1024)};
+    (void)lds_attrs;
+    *log2f_out = log2f; *log2t_out = log2t;
+}
+// k_score over the records in `hits`, by the queries' ranges (ws->d_qrange): ROWS rows of a tile; HEAVY: the queries that launch handed over
+template <int ROWS, bool HEAVY>
+static void launch_score(Batch& b, uint32_t grid, size_t lds, const uint64_t* hits, uint32_t sizes, uint32_t sb, const CandSlots& cs)
+{
+    hipLaunchKernelGGL((k_score<ROWS, HEAVY>), dim3(grid), dim3(WG), lds, b.st, hits, (const uint64_t*)b.ws->d_qrange, b.d_opts, sizes, sb, b.ws->d_cands[0],
+                       (uint64_t)b.ws->cap_cands, b.ws->d_counters, (uint64_t)0, cs.qcand, cs.qcand_n, cs.heavy, b.cancel);
+}
 
-    uint32_t up_chunks = 0, up_q[Workspace::UP_CHUNKS + 1] = {0};      // (a chunked upload: the pieces' query ranges)
-    auto upload_piece = [&](uint32_t c) -> int {                       // piece c of the batch's hashes, on the copy stream; its event behind it
-        const uint64_t h0 = offsets[up_q[c]] - base, h1 = offsets[up_q[c + 1]] - base;
-        if (h1 > h0) FPX_HIP(hipMemcpyAsync(ws->d_hashes + h0, hashes + base + h0, (h1 - h0) * sizeof(uint32_t), hipMemcpyHostToDevice, ws->copy_stream));
-        FPX_HIP(hipEventRecord(ws->ev_chunk[c], ws->copy_stream));
+// ---- the batch's way to the device -------------------------------------------------------------------------------------------------
+// piece c of a chunked upload's hashes, on the copy stream; its event behind it
+static int upload_piece(Batch& b, uint32_t c)
+{
+    Workspace* ws = b.ws;
+    const uint64_t h0 = b.offsets[b.up_q[c]] - b.base, h1 = b.offsets[b.up_q[c + 1]] - b.base;
+    if (h1 > h0) FPX_HIP(hipMemcpyAsync(ws->d_hashes + h0, b.hashes + b.base + h0, (h1 - h0) * sizeof(uint32_t), hipMemcpyHostToDevice, ws->copy_stream));
+    FPX_HIP(hipEventRecord(ws->ev_chunk[c], ws->copy_stream));
+    return FPX_OK;
+}
+// the batch: resident in HBM already, or uploaded from the caller's host buffers (query_wg: the batch goes to k_search_query)
+static int place_batch(Batch& b, bool query_wg)
+{
+    Workspace* ws = b.ws; hipStream_t st = b.st; const uint32_t B = b.B; const uint64_t P = b.P, base = b.base; int rc;
+    if (b.resident) {
+        b.d_hashes_base = b.resident->d_hashes;
+        b.d_offsets = b.resident->d_offsets + b.q0;
+        b.d_opts = b.resident->d_opts + (size_t)b.q0 * 4;
         return FPX_OK;
-    };
-    if (!single_fast) FPX_HIP(hipEventRecord(ws->ev_begin, st));
-    if (resident) {
-        d_hashes_base = resident->d_hashes;
-        d_offsets = resident->d_offsets + q0;
-        d_opts = resident->d_opts + (size_t)q0 * 4;
-    } else if (B == 1 && 32 + P * sizeof(uint32_t) <= STAGE_BYTES) {
+    }
+    if (B == 1 && 32 + P * sizeof(uint32_t) <= STAGE_BYTES) {
         // one small query: offsets, options and hashes travel in a single copy from pinned memory, no host sync
         if (!ws->h_stage) {
             FPX_HIP(hipHostMalloc(reinterpret_cast<void**>(&ws->h_stage), STAGE_BYTES, hipHostMallocMapped));
             FPX_HIP(hipHostGetDevicePointer(reinterpret_cast<void**>(&ws->d_stage), ws->h_stage, 0));
         }
         std::vector<uint32_t> h_opts;
-        fill_opts(h_opts, opts, offsets, 1);
+        fill_opts(h_opts, b.opts, b.offsets, 1);
         uint64_t* so = reinterpret_cast<uint64_t*>(ws->h_stage);
         so[0] = 0; so[1] = P;
         std::memcpy(ws->h_stage + 16, h_opts.data(), 16);
-        if (P) std::memcpy(ws->h_stage + 32, hashes + base, P * sizeof(uint32_t));
+        if (P) std::memcpy(ws->h_stage + 32, b.hashes + base, P * sizeof(uint32_t));
         // the kernels read the query straight from pinned host memory (4 KB over PCIe): no copy call
-        d_hashes_base = reinterpret_cast<const uint32_t*>(ws->d_stage + 32);
-        d_offsets = reinterpret_cast<const uint64_t*>(ws->d_stage);
-        d_opts = reinterpret_cast<const uint32_t*>(ws->d_stage + 16);
-        staged_single = true;
+        b.d_hashes_base = reinterpret_cast<const uint32_t*>(ws->d_stage + 32);
+        b.d_offsets = reinterpret_cast<const uint64_t*>(ws->d_stage);
+        b.d_opts = reinterpret_cast<const uint32_t*>(ws->d_stage + 16);
+        b.staged_single = true;
+        return FPX_OK;
+    }
+    if ((rc = grow(&ws->d_hashes, &ws->cap_hashes, (size_t)P + 1))) return rc;
+    std::vector<uint32_t>& h_opts = ws->h_opts;
+    fill_opts(h_opts, b.opts, b.offsets, B);
+    if (query_wg && B >= 1024u && P >= (1u << 20)) {
+        // A large batch for k_search_query: every query is a workgroup's own business, so the batch is uploaded in pieces on a stream of
+        // its own and the kernel over piece c waits for THAT piece only -- piece c + 1 crosses PCIe under it (33 MB per batch of
+        // 8192 x 1000 hashes: 0.6 ms of link time next to 0.45 ms of kernel).  Nothing here waits: the options live in the workspace.
+        if (!ws->copy_stream) {
+            FPX_HIP(hipStreamCreateWithFlags(&ws->copy_stream, hipStreamNonBlocking));
+            for (hipEvent_t& e : ws->ev_chunk) FPX_HIP(hipEventCreateWithFlags(&e, hipEventDisableTiming));
+        }
+        hipStream_t cs = ws->copy_stream;
+        FPX_HIP(hipMemcpyAsync(ws->d_offsets, b.offsets, ((size_t)B + 1) * sizeof(uint64_t), hipMemcpyHostToDevice, cs));
+        FPX_HIP(hipMemcpyAsync(ws->d_opts, h_opts.data(), h_opts.size() * sizeof(uint32_t), hipMemcpyHostToDevice, cs));
+        b.up_chunks = Workspace::UP_CHUNKS;
+        for (uint32_t c = 0; c <= b.up_chunks; ++c) b.up_q[c] = (uint32_t)((uint64_t)B * c / b.up_chunks);
+        // (the first piece now, piece c + 1 right after the kernel over piece c has been launched: a copy out of PAGEABLE memory keeps the
+        // calling thread until the runtime has staged it -- with all four enqueued here the first kernel started when the last piece had
+        // been staged, 6.1 M queries/s with one caller; page-locked sources do not care)
+        if ((rc = upload_piece(b, 0u))) return rc;
     } else {
-        if ((rc = grow(&ws->d_hashes, &ws->cap_hashes, (size_t)P + 1))) return rc;
-        std::vector<uint32_t>& h_opts = ws->h_opts;
-        fill_opts(h_opts, opts, offsets, B);
-        if (qs_path && B >= 1024u && P >= (1u << 20)) {
-            // A large batch for k_search_query: every query is a workgroup's own business, so the batch is uploaded in pieces on a stream of
-            // its own and the kernel over piece c waits for THAT piece only -- piece c + 1 crosses PCIe under it (33 MB per batch of
-            // 8192 x 1000 hashes: 0.6 ms of link time next to 0.45 ms of kernel).  Nothing here waits: the options live in the workspace.
-            if (!ws->copy_stream) {
-                FPX_HIP(hipStreamCreateWithFlags(&ws->copy_stream, hipStreamNonBlocking));
-                for (hipEvent_t& e : ws->ev_chunk) FPX_HIP(hipEventCreateWithFlags(&e, hipEventDisableTiming));
-            }
-            hipStream_t cs = ws->copy_stream;
-            FPX_HIP(hipMemcpyAsync(ws->d_offsets, offsets, ((size_t)B + 1) * sizeof(uint64_t), hipMemcpyHostToDevice, cs));
-            FPX_HIP(hipMemcpyAsync(ws->d_opts, h_opts.data(), h_opts.size() * sizeof(uint32_t), hipMemcpyHostToDevice, cs));
-            up_chunks = Workspace::UP_CHUNKS;
-            for (uint32_t c = 0; c <= up_chunks; ++c) up_q[c] = (uint32_t)((uint64_t)B * c / up_chunks);
-            // (the first piece now, piece c + 1 right after the kernel over piece c has been launched: a copy out of PAGEABLE memory keeps the
-            // calling thread until the runtime has staged it -- with all four enqueued here the first kernel started when the last piece had
-            // been staged, 6.1 M queries/s with one caller; page-locked sources do not care)
-            if ((rc = upload_piece(0u))) return rc;
-            d_hashes_base = ws->d_hashes - base;
-            d_offsets = ws->d_offsets;
-            d_opts = ws->d_opts;
-        } else {
         // (pageable sources go through the runtime's own staging.  A private page-locked ring per workspace was tried in round 3:
         // 3.8 / 5.2 M queries/s with one / two callers against 4.6 / 6.5 M this way -- the host's extra copy costs more than the
         // runtime's lock; what round 2 measured as "two pageable callers serialise" was the second caller's workspace being
         // allocated inside the timed loop)
-        if (P) FPX_HIP(hipMemcpyAsync(ws->d_hashes, hashes + base, P * sizeof(uint32_t), hipMemcpyHostToDevice, st));
-        FPX_HIP(hipMemcpyAsync(ws->d_offsets, offsets, ((size_t)B + 1) * sizeof(uint64_t), hipMemcpyHostToDevice, st));
+        if (P) FPX_HIP(hipMemcpyAsync(ws->d_hashes, b.hashes + base, P * sizeof(uint32_t), hipMemcpyHostToDevice, st));
+        FPX_HIP(hipMemcpyAsync(ws->d_offsets, b.offsets, ((size_t)B + 1) * sizeof(uint64_t), hipMemcpyHostToDevice, st));
         FPX_HIP(hipMemcpyAsync(ws->d_opts, h_opts.data(), h_opts.size() * sizeof(uint32_t), hipMemcpyHostToDevice, st));
         FPX_HIP(hipStreamSynchronize(st));             // (the caller's arrays may go once the call returns an error further down)
-        d_hashes_base = ws->d_hashes - base;
-        d_offsets = ws->d_offsets;
-        d_opts = ws->d_opts;
-        }
     }
-    // deferred-probe lists of the lean kernel: room for 1/8 of the pairs per segment (typically < 2 % are deferred)
-    const size_t def_cap = std::max<size_t>(4096, (size_t)(P / 8));
-    if (snap->n_lean || snap->n_direct || side_path) {          // (k_search_side: the statistics sets behind the counts)
-        const size_t need = def_cap * std::max(1u, snap->n_lean);
+    b.d_hashes_base = ws->d_hashes - base;
+    b.d_offsets = ws->d_offsets;
+    b.d_opts = ws->d_opts;
+    return FPX_OK;
+}
+// deferred-probe lists of the lean kernel: room for 1/8 of the pairs per segment (typically < 2 % are deferred)
+static int ensure_def_lists(Batch& b, bool side_wg)
+{
+    Snapshot* snap = b.snap; Workspace* ws = b.ws; int rc;
+    b.def_cap = std::max<size_t>(4096, (size_t)(b.P / 8));
+    if (snap->n_lean || snap->n_direct || side_wg) {            // (k_search_side: the statistics sets behind the counts)
+        const size_t need = b.def_cap * std::max(1u, snap->n_lean);
         if ((rc = grow(&ws->d_def_list, &ws->cap_def, need))) return rc;
         if (snap->n_lean > ws->cap_def_segs || !ws->d_def_count) {
             if (ws->d_def_count) (void)hipFree(ws->d_def_count);
@@ -579,12 +667,227 @@ static int run_batch(Snapshot* snap, Workspace* ws, const QueryBatch* resident, 
         }
     }
     // (for the workspace's capacity, not this snapshot's n_lean: the layout must not move between batches)
-    const size_t def_stat_off = (size_t)ws->cap_def_segs * DEF_COUNT_STRIDE;
-    const size_t def_words = def_stat_off + LEAN_STAT_WORDS;
-    // (every memset is a 5-us launch of its own: the batch's zeroing rides in kernels that run anyway where it can)
+    b.def_stat_off = (size_t)ws->cap_def_segs * DEF_COUNT_STRIDE;
+    b.def_words = b.def_stat_off + LEAN_STAT_WORDS;
+    return FPX_OK;
+}
 
-    // ---- 1+2: keys, sort by (hash, q)
-    int kcur = 0;
+// ---- the query-per-workgroup paths: who takes them --------------------------------------------------------------------------------
+// the queries' rule: short enough for the kernels' hash set, and a floor above the legacy protocol's
+static bool queries_fit_wg(const uint64_t* offsets, const fpx_opts* opts, uint32_t B)
+{
+    for (uint32_t q = 0; q < B; ++q) {
+        const uint64_t raw_len = offsets[q + 1] - offsets[q];
+        if (raw_len > QS_MAX_HASHES || query_floor(opts[q], raw_len) <= 2u) return false;
+    }
+    return true;
+}
+// a group for k_search_query's filtered instantiation: superseded docs, or columns outside the snapshot
+static bool group_filtered(const GroupDesc& gd) { return gd.any_dead != 0u || gd.active != (gd.nseg >= 32u ? 0xFFFFFFFFu : ((1u << gd.nseg) - 1u)); }
+
+// ONE WORKGROUP PER QUERY (fpx_qsearch.hpp): the snapshot is one packed group and nothing else, every column of it searched, no superseded
+// docs -- the resident index between merges --, the queries short enough for their hash set and their floor above the legacy protocol's.
+// Option query_wg 2: a group with superseded docs or columns outside the snapshot too, by the kernel's filtered instantiation (*filt).
+static bool takes_query_wg(const Snapshot* snap, const uint64_t* offsets, const fpx_opts* opts, uint32_t B, bool* filt)
+{
+    const int64_t query_wg = ctx_opt(snap->ctx, OPT_QUERY_WG);
+    if (!(snap->n_file == 0 && snap->n_solo == 0 && snap->n_group == 1 && snap->n_direct != 0 &&
+          (snap->n_mem == 0 || snap->mem_items == 0 || snap->d_memtab != nullptr) && snap->groups[0]->packed && query_wg != 0)) return false;
+    *filt = group_filtered(snap->h_group[0]);
+    return (!*filt || query_wg == 2) && queries_fit_wg(offsets, opts, B);
+}
+// ... and the same for the file segments NEXT TO the group (fpx_qside.hpp; option side_wg = 1): a snapshot -- part 1 of a live one, or a
+// whole young index -- of small decoded and direct-addressed-alone segments only, none of them a hash-window slice, no group, no
+// memory-segment postings.  The queries' rule is parts_take's, so a batch in two parts never splits between paths by query.
+static bool takes_side_wg(const Snapshot* snap, const uint64_t* offsets, const fpx_opts* opts, uint32_t B)
+{
+    if (!(ctx_opt(snap->ctx, OPT_SIDE_WG) == 1 &&
+          snap->n_group == 0 && snap->n_lean == 0 && snap->n_gen == 0 && snap->n_file == snap->n_small && snap->n_direct == snap->n_solo &&
+          snap->n_small + snap->n_solo != 0 && (snap->n_mem == 0 || snap->mem_items == 0))) return false;
+    for (const SegDesc& d : snap->h_file) if (!(d.own_flags == 0u && d.items && d.sbucket && d.sfirst && d.scode)) return false;
+    for (const SegDesc& d : snap->h_direct) if (!(d.own_flags == 0u && d.drec && d.primary)) return false;
+    return queries_fit_wg(offsets, opts, B);
+}
+
+// ---- A. a query per workgroup --------------------------------------------------------------------------------------------------------
+// k_search_query's instantiations: columns of a directory line (8 | 16), per-query scan statistics, the memory segments' table, filtered
+static void launch_search_query(bool ns8, bool qs, bool mem, bool filt, dim3 grid, hipStream_t st, const QSearchArgs& qa, const GroupArgs& g)
+{
+#define FPX_LQ(NS, QSV, MEM, FILT) hipLaunchKernelGGL((k_search_query<NS, QSV, MEM, FILT>), grid, dim3(QS_WG), QS_LDS_BYTES, st, qa, g)
+#define FPX_LQ_MEM(NS, QSV, FILT) do { if (mem) FPX_LQ(NS, QSV, true, FILT); else FPX_LQ(NS, QSV, false, FILT); } while (0)
+#define FPX_LQ_QS(NS, FILT) do { if (qs) FPX_LQ_MEM(NS, true, FILT); else FPX_LQ_MEM(NS, false, FILT); } while (0)
+#define FPX_LQ_NS(FILT) do { if (ns8) FPX_LQ_QS(8, FILT); else FPX_LQ_QS(16, FILT); } while (0)
+    if (filt) FPX_LQ_NS(true); else FPX_LQ_NS(false);
+#undef FPX_LQ_NS
+#undef FPX_LQ_QS
+#undef FPX_LQ_MEM
+#undef FPX_LQ
+}
+// ... and k_search_classes'
+static void launch_search_classes(bool ns8, bool mem, dim3 grid, hipStream_t st, const QSearchArgs& qa, const GroupArgs& g)
+{
+#define FPX_LC(NS, MEM) hipLaunchKernelGGL((k_search_classes<NS, MEM>), grid, dim3(QS_WG), QS_LDS_BYTES, st, qa, g)
+    if (ns8) { if (mem) FPX_LC(8, true); else FPX_LC(8, false); }
+    else { if (mem) FPX_LC(16, true); else FPX_LC(16, false); }
+#undef FPX_LC
+}
+// the end of a query-per-workgroup path: results, the kernel's statistics sets, per-query statistics, the next batch's hints
+static int finish_wg_path(Batch& b, const ResultsTo& to, uint64_t Cf, uint32_t path_bits)
+{
+    Workspace* ws = b.ws; int rc;
+    if (!b.partial && (rc = deliver_results(ws, b.B, b.out_cap, to.staged, b.out, b.out_n, b.st))) return rc;
+    const unsigned long long* ls = host_stat_sets(b);
+    const StatSums s = sum_stat_sets(ls);
+    gather_hist(ws->batch_hist, ws->h_counters, ls, s.probes);
+    if (fpx_stats* stats = b.stats) {
+        float ms = 0.f, total_ms = 0.f;
+        (void)hipEventElapsedTime(&ms, ws->ev_probe0, ws->ev_probe1);
+        (void)hipEventElapsedTime(&total_ms, ws->ev_begin, ws->ev_end);
+        stats->probes += s.probes; stats->scanned_blocks += s.blocks; stats->scanned_docs += s.docs; stats->hits += s.records;
+        stats->algorithmic_bytes += s.blocks * 512ull + s.bytes_off;
+        stats->candidates += Cf + ws->h_counters[CTR_SLOTCANDS];
+        stats->probe_kernel_ms += ms; stats->total_gpu_ms += total_ms; stats->probe_launches += 1;
+        stats->probe_kernel_bytes += s.blocks * 512ull + s.bytes_off;
+        stats->probe_kernel_fetched_bytes += (s.dreads + 1) / 2 * 128ull;
+        stats->path_flags |= 1u | (Cf ? 2u : 0u) | path_bits;
+    }
+    if ((rc = deliver_qstats(b))) return rc;
+    ws->hint_P = b.P; ws->hint_H = std::max<uint64_t>(s.records, 1);          // (sizes the pipeline's bins should a later batch take it)
+    ws->hint_misc = 0; ws->hint_def = 0;
+    return FPX_OK;
+}
+// Option hot_wg: the R queries whose records outgrew the LDS array were named in the redo list, with nothing counted and no candidate;
+// k_search_classes searches each of them once per doc class (fpx_qsearch.hpp), into the same slots and shared list.  A few of them: the
+// batch stays here and nothing backs off.  More than qs_redo_limit(B): the pipeline and the back-off, as before -- a walk per class
+// costs more than the pipeline's one once much of a batch is hot, and hot traffic comes in runs.
+static int redo_hot_queries(Batch& b, QSearchArgs qa, const GroupArgs& gargs, bool ns8, int cus, uint64_t R)
+{
+    if (R > qs_redo_limit(b.B) || R > qa.redo_cap) {
+        __atomic_store_n(&b.snap->qs_skip, 32u, __ATOMIC_RELAXED);
+        return FPX_REDO_QS;
+    }
+    int rc;
+    qa.q_begin = 0u; qa.q_end = (uint32_t)R; qa.next_q = nullptr; qa.stagger = 0u;      // (entries of the list; all pieces of a chunked upload have arrived)
+    launch_search_classes(ns8, qa.mem_tab != nullptr, dim3(std::min<uint32_t>((uint32_t)R, (uint32_t)cus * QS_WGS_PER_CU)), b.st, qa, gargs);
+    if ((rc = publish(b, true))) return rc;
+    FPX_HIP(hipEventRecord(b.ws->ev_end, b.st));
+    FPX_SYNC_BATCH(b);
+    return handed_back(b.ws, b.snap) ? FPX_REDO_QS : FPX_OK;
+}
+
+// Dedup, probe, count and floor happen in ONE kernel, no keys are made or ordered, no record reaches HBM.  A batch that kernel hands back
+// (hot hashes: a query's records outgrow its LDS array) returns FPX_REDO_QS: run_with_redos gives it to the pipeline.
+static int run_query_wg(Batch& b, bool filt)
+{
+    Snapshot* snap = b.snap; Workspace* ws = b.ws; hipStream_t st = b.st; const uint32_t B = b.B; int rc;
+    const bool ns8 = snap->groups[0]->ns == 8u;
+    // (option hot_wg = 1, unfiltered: the batch's redo list -- B entries, behind the slots and their counts)
+    const bool hot_wg = !filt && ctx_opt(snap->ctx, OPT_HOT_WG) == 1;
+    CandSlots cs;
+    if ((rc = ensure_cand_slots(ws, B, hot_wg ? (size_t)B : 0, &cs))) return rc;
+    const uint32_t sbf = 32u - b.qb;
+    hipLaunchKernelGGL(k_qs_zero, dim3(8), dim3(256), 0, st, ws->d_counters, ws->d_def_count, (uint32_t)b.def_words);
+    FPX_HIP(hipEventRecord(ws->ev_probe0, st));
+    struct Running {                                 // batches of this context inside their k_search_query launches, this one included
+        std::atomic<int>* c; int before;
+        explicit Running(std::atomic<int>* c_) : c(c_), before(c_->fetch_add(1)) {}
+        ~Running() { c->fetch_sub(1); }
+    } running(&snap->ctx->qs_running);
+    const bool alone = running.before == 0;
+    QSearchArgs qa{};
+    qa.hashes_base = b.d_hashes_base; qa.offsets = b.d_offsets; qa.opts = b.d_opts; qa.q_begin = 0u; qa.q_end = B; qa.sb = sbf;
+    qa.cands = ws->d_cands[0]; qa.cand_cap = ws->cap_cands; qa.qcand = cs.qcand; qa.qcand_n = cs.qcand_n;
+    qa.counters = ws->d_counters; qa.stat_sets = device_stat_sets(b);
+    qa.qstats = b.want_q ? ws->d_qstats : nullptr; qa.cancel = b.cancel;
+    if (snap->n_mem != 0 && snap->mem_items != 0) { qa.mem_tab = snap->d_memtab; qa.mem_bucket = snap->d_membucket; qa.mem_bits = snap->d_membits; }
+    if (hot_wg) { qa.redo = reinterpret_cast<unsigned long long*>(cs.extra); qa.redo_cap = B; }
+    const GroupArgs gargs{snap->h_group[0], snap->d_direct};
+    // as many workgroups as the chip holds at once (LDS: QS_WGS_PER_CU per CU); each takes every gridDim.x-th query
+    const int cus = device_cus(snap->ctx);
+    const uint32_t up_chunks = b.up_chunks;
+    for (uint32_t c = 0; c < std::max(1u, up_chunks); ++c) {
+        qa.q_begin = up_chunks ? b.up_q[c] : 0u; qa.q_end = up_chunks ? b.up_q[c + 1] : B;
+        if (qa.q_end == qa.q_begin) { if (up_chunks && c + 1u < up_chunks && (rc = upload_piece(b, c + 1u))) return rc; continue; }
+        // (alone on the device: the launch's queue of queries -- a word of the deferred lists' counts, zeroed by k_qs_zero, unused on this
+        // path -- and a staggered start; next to other batches' kernels neither: fpx_qsearch.hpp says why)
+        qa.next_q = (FPX_QS_DYN && alone) ? ws->d_def_count + c : nullptr;
+        qa.stagger = alone ? QS_STAGGER : 0u;
+        if (up_chunks) FPX_HIP(hipStreamWaitEvent(st, ws->ev_chunk[c], 0));           // (the piece's hashes have arrived; the next piece is on its way)
+        launch_search_query(ns8, b.want_q, qa.mem_tab != nullptr, filt, dim3(std::min<uint32_t>(qa.q_end - qa.q_begin, (uint32_t)cus * QS_WGS_PER_CU)), st, qa, gargs);
+        if (up_chunks && c + 1u < up_chunks && (rc = upload_piece(b, c + 1u))) return rc;       // (the next piece crosses PCIe under this kernel)
+    }
+    FPX_HIP(hipGetLastError());
+    FPX_HIP(hipEventRecord(ws->ev_probe1, st));
+    ResultsTo to;
+    if ((rc = results_target(b, &to))) return rc;
+    launch_finish(b, ws->d_cands[0], 0, sbf, cs, to.res, to.n, b.stats != nullptr);
+    // (the batch's counters and statistics sets into the host's mapped copies: after the first pass, and again after a redo)
+    if ((rc = publish(b, true))) return rc;
+    FPX_HIP(hipEventRecord(ws->ev_end, st));
+    FPX_SYNC_BATCH(b);
+#ifdef FPX_QS_PROF
+    fprintf(stderr, "qs_prof clocks/query: setup %.0f dedup %.0f rounds %.0f tasks %.0f count+exact %.0f handover %.0f", ws->h_counters[CTR_HIST] / (double)B, ws->h_counters[CTR_HIST + 1] / (double)B,
+            ws->h_counters[CTR_HIST + 2] / (double)B, ws->h_counters[CTR_HIST + 3] / (double)B, ws->h_counters[CTR_HIST + 4] / (double)B, ws->h_counters[CTR_HIST + 5] / (double)B);
+    // (the finer marks: waits inside dedup, the rounds and before the tasks)
+    fprintf(stderr, " | dedup: hash wait %.0f | rounds: hash wait %.0f heads wait %.0f words wait %.0f probe %.0f | next offsets wait %.0f\n", ws->h_counters[CTR_HIST + 6] / (double)B,
+            ws->h_counters[CTR_HIST + 7] / (double)B, ws->h_counters[CTR_HIST + 8] / (double)B, ws->h_counters[CTR_HIST + 9] / (double)B, ws->h_counters[CTR_HIST + 10] / (double)B,
+            ws->h_counters[CTR_HIST + 11] / (double)B);
+#endif
+    if (handed_back(ws, snap)) return FPX_REDO_QS;
+    // (the shared list's length is known to the host only behind a synchronisation of its own: the sort below needs it)
+    const uint64_t R = hot_wg ? ws->h_counters[CTR_REDO] : 0;
+    if (R != 0 && (rc = redo_hot_queries(b, qa, gargs, ns8, cus, R))) return rc;
+    // some queries have more candidates than slots: the second k_finish, which also takes the redone queries' candidates from their slots
+    uint64_t Cf = 0;
+    if (ws->h_counters[CTR_CANDS] != 0 || R != 0) {
+        Cf = ws->h_counters[CTR_CANDS];
+        if ((rc = finish_crowded(b, sbf, cs, to, Cf))) return rc;
+    }
+    return finish_wg_path(b, to, Cf, 4u | 64u | (filt ? 256u : 0u) | (R != 0 ? 1024u : 0u));
+}
+
+// ... and the file segments next to the group, by k_search_side
+static int run_side_wg(Batch& b)
+{
+    Snapshot* snap = b.snap; Workspace* ws = b.ws; hipStream_t st = b.st; const uint32_t B = b.B; int rc;
+    CandSlots cs;
+    if ((rc = ensure_cand_slots(ws, B, 0, &cs))) return rc;
+    const uint32_t sbf = 32u - b.qb;
+    hipLaunchKernelGGL(k_qs_zero, dim3(8), dim3(256), 0, st, ws->d_counters, ws->d_def_count, (uint32_t)b.def_words);
+    FPX_HIP(hipEventRecord(ws->ev_probe0, st));
+    SideArgs sa{};
+    sa.hashes_base = b.d_hashes_base; sa.offsets = b.d_offsets; sa.opts = b.d_opts; sa.B = B; sa.sb = sbf;
+    sa.cands = ws->d_cands[0]; sa.cand_cap = ws->cap_cands; sa.qcand = cs.qcand; sa.qcand_n = cs.qcand_n;
+    sa.counters = ws->d_counters; sa.stat_sets = device_stat_sets(b);
+    sa.qstats = b.want_q ? ws->d_qstats : nullptr; sa.cancel = b.cancel;
+    sa.small = snap->d_small; sa.n_small = snap->n_small; sa.solo = snap->d_solo; sa.n_solo = snap->n_solo;
+    // as many workgroups as the chip holds at once (LDS: SIDE_WGS_PER_CU per CU); each takes every gridDim.x-th query
+    const int cus = device_cus(snap->ctx);
+    hipLaunchKernelGGL(k_search_side, dim3(std::min<uint32_t>(B, (uint32_t)cus * SIDE_WGS_PER_CU)), dim3(SIDE_WG), SIDE_LDS_BYTES, st, sa);
+    FPX_HIP(hipGetLastError());
+    FPX_HIP(hipEventRecord(ws->ev_probe1, st));
+    ResultsTo to;
+    if ((rc = results_target(b, &to))) return rc;
+    launch_finish(b, ws->d_cands[0], 0, sbf, cs, to.res, to.n, b.stats != nullptr);
+    if ((rc = publish(b, true))) return rc;
+    FPX_HIP(hipEventRecord(ws->ev_end, st));
+    FPX_SYNC_BATCH(b);
+    if (handed_back(ws, snap)) return FPX_REDO_QS;           // (that snapshot or part alone: run_with_redos)
+    const uint64_t Cf = ws->h_counters[CTR_CANDS];
+    if (Cf != 0 && (rc = finish_crowded(b, sbf, cs, to, Cf))) return rc;
+    return finish_wg_path(b, to, Cf, 512u);
+}
+
+// ---- B. the pipeline: steps of its three drivers ----------------------------------------------------------------------------------------
+// the batch's (hash, q) keys, ordered; flagged: duplicates were flagged where the keys were made; key_skip: low hash bits the order ignores
+struct Keys { const uint64_t* d_pairs; bool flagged; uint32_t key_skip; };
+
+// ---- 1+2: keys, sort by (hash, q)
+static int make_keys(Batch& b, bool single_fast, bool score_only, Keys* keys)
+{
+    Snapshot* snap = b.snap; Workspace* ws = b.ws; hipStream_t st = b.st; const uint64_t* offsets = b.offsets;
+    const uint32_t B = b.B; const uint64_t P = b.P, base = b.base; const unsigned qb = b.qb;
+    int rc, kcur = 0;
     // (every kernel of the batch must look back over the same bucket width: the coarser order only where the direct-addressed
     // kernels, which take it as a parameter, are the only ones that read the pairs)
     // Snapshots of direct-addressed segments only (their kernels are the only readers of the pairs): duplicates are flagged
@@ -597,14 +900,14 @@ static int run_batch(Snapshot* snap, Workspace* ws, const QueryBatch* resident, 
     const uint32_t key_skip = flagged ? KEY_SORT_SKIP_DIRECT : KEY_SORT_SKIP;      // (flagged keys: the top 8 hash bits -- 8 / 7 / 6 bits measured alike, 5 / 4 slower: round 5)
     // small batches sort their keys per query in ONE kernel (k_make_keys_sorted) instead of batch-wide in eleven launches
     const uint64_t local_sort_max = (uint64_t)std::max<int64_t>(0, ctx_opt(snap->ctx, OPT_LOCAL_SORT_MAX));
-    bool local_sort = P && !score_only && !single_fast && !flagged && !qs_path && !side_path && B >= 2u && P <= local_sort_max && snap->n_small == 0;
+    bool local_sort = P && !score_only && !single_fast && !flagged && B >= 2u && P <= local_sort_max && snap->n_small == 0;
     if (local_sort)
         for (uint32_t q = 0; q < B && local_sort; ++q) local_sort = offsets[q + 1] - offsets[q] <= QSORT_MAX;
     if (local_sort) {
-        hipLaunchKernelGGL(k_make_keys_sorted, dim3(B), dim3(256), 0, st, d_hashes_base, d_offsets, B, qb, base, ws->d_keys[0],
-                           (snap->n_lean || snap->n_direct) ? ws->d_def_count : nullptr, (uint32_t)def_words);
+        hipLaunchKernelGGL(k_make_keys_sorted, dim3(B), dim3(256), 0, st, b.d_hashes_base, b.d_offsets, B, qb, base, ws->d_keys[0],
+                           (snap->n_lean || snap->n_direct) ? ws->d_def_count : nullptr, (uint32_t)b.def_words);
         FPX_HIP(hipGetLastError());
-    } else if (P && !score_only && !qs_path && !side_path) {
+    } else if (P && !score_only) {
         // flagged keys are brought into (hash bucket, query) order by our own counting sort, whose counts k_make_keys_dedup takes
         // on its way (fpx_keyorder.hpp); tiny batches stay in query order (the three launches cost what the order buys)
         const uint64_t order_min = (uint64_t)std::max<int64_t>(0, ctx_opt(snap->ctx, OPT_ORDER_MIN_PAIRS));
@@ -614,12 +917,13 @@ static int run_batch(Snapshot* snap, Workspace* ws, const QueryBatch* resident, 
         const uint64_t order_max = 1ull << 20;
         const bool own_order = flagged && !single_fast && P >= order_min && P <= order_max;
         if (own_order && (rc = key_order_setup(ws, B, 0u, 32u - key_skip, &ko, nullptr, st, B >= KO_ROWS_MIN_B))) return rc;
+        const uint64_t key_base = b.staged_single ? 0ull : base;
         if (flagged)
-            hipLaunchKernelGGL(k_make_keys_dedup, dim3(B), dim3(256), 0, st, d_hashes_base, d_offsets, B, qb, staged_single ? 0ull : base, ws->d_keys[0],
-                               single_fast ? ws->d_counters : nullptr, ws->d_def_count, (uint32_t)def_words, ko);
+            hipLaunchKernelGGL(k_make_keys_dedup, dim3(B), dim3(256), 0, st, b.d_hashes_base, b.d_offsets, B, qb, key_base, ws->d_keys[0],
+                               single_fast ? ws->d_counters : nullptr, ws->d_def_count, (uint32_t)b.def_words, ko);
         else
-            hipLaunchKernelGGL(k_make_keys, dim3(B), dim3(256), 0, st, d_hashes_base, d_offsets, B, qb, staged_single ? 0ull : base, ws->d_keys[0],
-                               single_fast ? ws->d_counters : nullptr, (snap->n_lean || snap->n_direct) ? ws->d_def_count : nullptr, (uint32_t)def_words);
+            hipLaunchKernelGGL(k_make_keys, dim3(B), dim3(256), 0, st, b.d_hashes_base, b.d_offsets, B, qb, key_base, ws->d_keys[0],
+                               single_fast ? ws->d_counters : nullptr, (snap->n_lean || snap->n_direct) ? ws->d_def_count : nullptr, (uint32_t)b.def_words);
         // k_make_keys writes the pairs in (q, position) order and the LSD radix sort is stable, so sorting on the 32 hash
         // bits alone leaves the pairs ordered by (hash, q): equal pairs end up adjacent without sorting the q bits.
         // ... and only the top 32 - KEY_SORT_SKIP of them: block-level locality is all the probes need from the order
@@ -631,981 +935,448 @@ static int run_batch(Snapshot* snap, Workspace* ws, const QueryBatch* resident, 
         if (own_order) {
             if (ko.qrows) hipLaunchKernelGGL(k_group_hist, dim3((B + KO_GROUP - 1u) / KO_GROUP), dim3(256), 0, st, ko, B);
             hipLaunchKernelGGL(k_bucket_scan, dim3(ko.nb), dim3(256), 0, st, ko, (B + KO_GROUP - 1u) / KO_GROUP);
-            hipLaunchKernelGGL(k_scatter_keys, dim3((B + KO_GROUP - 1u) / KO_GROUP), dim3(256), 0, st, ko, (const uint64_t*)ws->d_keys[0], d_offsets, staged_single ? 0ull : base, 0u, B, qb,
+            hipLaunchKernelGGL(k_scatter_keys, dim3((B + KO_GROUP - 1u) / KO_GROUP), dim3(256), 0, st, ko, (const uint64_t*)ws->d_keys[0], b.d_offsets, key_base, 0u, B, qb,
                                ws->d_keys[1], (unsigned long long*)nullptr);
             FPX_HIP(hipGetLastError());
             kcur = 1;
         } else if (!(flagged && P <= local_sort_max)) {
-            const size_t tb = sort_u64_temp_bytes(P, qb + key_skip, 32 + qb);
-            if ((rc = grow(reinterpret_cast<uint8_t**>(&ws->d_temp), &ws->cap_temp, tb + 256))) return rc;
-            FPX_HIP(sort_u64(ws->d_temp, ws->cap_temp, ws->d_keys[0], ws->d_keys[1], P, qb + key_skip, 32 + qb, st, &kcur));
+            if ((rc = sort_keys(ws, ws->d_keys, P, qb + key_skip, 32 + qb, st, &kcur))) return rc;
         }
     }
-    const uint64_t* d_pairs = ws->d_keys[kcur];
+    keys->d_pairs = ws->d_keys[kcur];
+    keys->flagged = flagged;
+    keys->key_skip = key_skip;
+    return FPX_OK;
+}
 
-    // per-query scan statistics, when the caller asked for them (a single query's are the call's totals: search_split)
-    const bool want_q = (q_blocks || q_docs) && B >= 2u && !score_only;
-    if (want_q && (rc = grow(&ws->d_qstats, &ws->cap_qstats, (size_t)B + 1))) return rc;
-    auto deliver_qstats = [&]() -> int {
-        if (!want_q) return FPX_OK;
-        std::vector<unsigned long long> hq(B);
-        FPX_HIP(hipMemcpy(hq.data(), ws->d_qstats, (size_t)B * sizeof(unsigned long long), hipMemcpyDeviceToHost));
-        for (uint32_t q = 0; q < B; ++q) {
-            if (q_blocks) q_blocks[q] = hq[q] & 0xFFFFFFFFull;
-            if (q_docs) q_docs[q] = hq[q] >> 32;
-        }
-        return FPX_OK;
-    };
-    if (qs_path) {
-        const GroupDesc& gd = snap->h_group[0];
-        const Group* grp = snap->groups[0].get();
-        // (option hot_wg = 1, unfiltered: the batch's redo list -- B entries, behind the slots and their counts)
-        const bool hot_wg = !qs_filt && ctx_opt(snap->ctx, OPT_HOT_WG) == 1;
-        const size_t qcand_words = (size_t)B * QCAND_SLOTS + 2 * ((size_t)B / 2 + 1);
-        if ((rc = grow(&ws->d_qcand, &ws->cap_qcand, qcand_words + (hot_wg ? (size_t)B : 0)))) return rc;
-        uint64_t* d_qcand = ws->d_qcand;
-        uint32_t* d_qcand_n = reinterpret_cast<uint32_t*>(ws->d_qcand + (size_t)B * QCAND_SLOTS);
-        const size_t cand_guess0 = std::max<size_t>(1u << 16, (size_t)B * 64);
-        if (ws->cap_cands < cand_guess0 && (rc = grow_pair(ws->d_cands, &ws->cap_cands, cand_guess0))) return rc;
-        const uint32_t sbf = 32u - qb;
-        hipLaunchKernelGGL(k_qs_zero, dim3(8), dim3(256), 0, st, ws->d_counters, ws->d_def_count, (uint32_t)def_words);
-        FPX_HIP(hipEventRecord(ws->ev_probe0, st));
-        struct Running {                                 // batches of this context inside their k_search_query launches, this one included
-            std::atomic<int>* c; int before;
-            explicit Running(std::atomic<int>* c_) : c(c_), before(c_->fetch_add(1)) {}
-            ~Running() { c->fetch_sub(1); }
-        } running(&snap->ctx->qs_running);
-        const bool alone = running.before == 0;
-        QSearchArgs qa{};
-        qa.hashes_base = d_hashes_base; qa.offsets = d_offsets; qa.opts = d_opts; qa.q_begin = 0u; qa.q_end = B; qa.sb = sbf;
-        qa.cands = ws->d_cands[0]; qa.cand_cap = ws->cap_cands; qa.qcand = d_qcand; qa.qcand_n = d_qcand_n;
-        qa.counters = ws->d_counters; qa.stat_sets = reinterpret_cast<unsigned long long*>(ws->d_def_count + def_stat_off);
-        qa.qstats = want_q ? ws->d_qstats : nullptr; qa.cancel = cancel;
-        if (snap->n_mem != 0 && snap->mem_items != 0) { qa.mem_tab = snap->d_memtab; qa.mem_bucket = snap->d_membucket; qa.mem_bits = snap->d_membits; }
-        if (hot_wg) { qa.redo = reinterpret_cast<unsigned long long*>(ws->d_qcand + qcand_words); qa.redo_cap = B; }
-        const GroupArgs gargs{gd, snap->d_direct};
-        // as many workgroups as the chip holds at once (LDS: QS_WGS_PER_CU per CU); each takes every gridDim.x-th query
-        static std::atomic<int> cus_of[64];
-        int cus = cus_of[(unsigned)snap->ctx->device & 63u].load(std::memory_order_relaxed);
-        if (cus == 0) {
-            if (hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, snap->ctx->device) != hipSuccess || cus <= 0) { (void)hipGetLastError(); cus = 256; }
-            cus_of[(unsigned)snap->ctx->device & 63u].store(cus, std::memory_order_relaxed);
-        }
-        for (uint32_t c = 0; c < std::max(1u, up_chunks); ++c) {
-            qa.q_begin = up_chunks ? up_q[c] : 0u; qa.q_end = up_chunks ? up_q[c + 1] : B;
-            if (qa.q_end == qa.q_begin) { if (up_chunks && c + 1u < up_chunks && (rc = upload_piece(c + 1u))) return rc; continue; }
-            // (alone on the device: the launch's queue of queries -- a word of the deferred lists' counts, zeroed by k_qs_zero, unused on this
-            // path -- and a staggered start; next to other batches' kernels neither: fpx_qsearch.hpp says why)
-            qa.next_q = (FPX_QS_DYN && alone) ? ws->d_def_count + c : nullptr;
-            qa.stagger = alone ? QS_STAGGER : 0u;
-            if (up_chunks) FPX_HIP(hipStreamWaitEvent(st, ws->ev_chunk[c], 0));           // (the piece's hashes have arrived; the next piece is on its way)
-            const dim3 qgrid(std::min<uint32_t>(qa.q_end - qa.q_begin, (uint32_t)cus * QS_WGS_PER_CU));
-            const bool mem = qa.mem_tab != nullptr;
-            auto launch = [&](auto kernel) { hipLaunchKernelGGL(kernel, qgrid, dim3(QS_WG), QS_LDS_BYTES, st, qa, gargs); };
-            if (qs_filt) {
-                if (grp->ns == 8u) {
-                    if (mem) { if (want_q) launch(k_search_query<8, true, true, true>); else launch(k_search_query<8, false, true, true>); }
-                    else { if (want_q) launch(k_search_query<8, true, false, true>); else launch(k_search_query<8, false, false, true>); }
-                } else {
-                    if (mem) { if (want_q) launch(k_search_query<16, true, true, true>); else launch(k_search_query<16, false, true, true>); }
-                    else { if (want_q) launch(k_search_query<16, true, false, true>); else launch(k_search_query<16, false, false, true>); }
+// the hit records' bins of the device-sized path (fpx_partition.hpp), as its probe kernels need them
+struct Bins {
+    BinArgs h{};
+    bool binned = false; uint32_t sbins = 0;      // k_probe_group bins the records itself, k_score_bin scores a bin per workgroup: that many
+    uint32_t ref_cap = 0;                         // references to hot lists a bin takes; 0: hot lists are copied into the bins
+    uint32_t* d_bin_count = nullptr; uint32_t* d_qcount = nullptr;
+    uint64_t est_H = 0;                           // the batch's records, as the workspace's last batch lets expect
+};
+// one round of probe launches: what the driver tells it, and what it reports
+struct Probes {
+    bool single_fast = false; int attempt = 0; bool force_generic = false;
+    const Bins* bins = nullptr;           // the device-sized path: the records go to d_hits[1] and the bins, nothing is copied to the host
+    bool used_lean = false, spread = false, used_fused = false; uint32_t launches = 0;
+};
+
+// ---- 3+4: probes, by the segments' storage forms
+static int launch_probes(Batch& b, const Keys& keys, Probes& pr)
+{
+    Snapshot* snap = b.snap; Workspace* ws = b.ws; hipStream_t st = b.st; const uint64_t P = b.P; const unsigned qb = b.qb;
+    const bool single_fast = pr.single_fast, fast = pr.bins != nullptr, binned = fast && pr.bins->binned;
+    uint64_t* const d_hits = ws->d_hits[fast ? 1 : 0];                            // (fast: binned into d_hits[0] afterwards)
+    const uint32_t key_skip = keys.flagged ? KEY_SKIP_FLAGGED : keys.key_skip;
+    pr.used_lean = false; pr.spread = false;
+    if (!single_fast) FPX_HIP(hipMemsetAsync(ws->d_counters, 0, CTR_COUNT * sizeof(unsigned long long), st));   // (k_make_keys did it)
+    if (b.want_q) FPX_HIP(hipMemsetAsync(ws->d_qstats, 0, (size_t)b.B * sizeof(unsigned long long), st));
+    if (P && (snap->n_file || snap->n_direct)) {
+        ProbeArgs a;
+        a.pairs = keys.d_pairs; a.P = P; a.qb = qb;
+        // enough workgroups to fill 256 CUs; long per-wave runs amortise the index walk for big batches
+        const uint64_t total = P * snap->n_file;
+        // (16 pairs per wave also for tiny batches: a single query is bound by per-workgroup set-up, not by parallelism)
+        a.ppw = total >= (1ull << 22) ? 64u : 16u;
+        a.rounds = total >= (1ull << 25) ? 2u : 1u;
+        a.bsp = ((snap->max_block_size + 15u) & ~15u) + 32u;
+        a.hits = d_hits; a.hit_cap = ws->cap_hits; a.counters = ws->d_counters;
+        a.def_list = ws->d_def_list; a.def_count = ws->d_def_count; a.def_cap = (uint32_t)b.def_cap; a.ctr_off = 0; a.lean_stats = nullptr; a.cancel = b.cancel;
+        a.key_skip = key_skip;
+        a.qstats = b.want_q ? ws->d_qstats : nullptr;
+        const uint64_t per_wg = (uint64_t)PWAVES * a.ppw * a.rounds;
+        const uint32_t gx = (uint32_t)((P + per_wg - 1) / per_wg);
+        const size_t lds = STAGE_CAP * sizeof(uint64_t) + sizeof(DecodeLut) + (size_t)PWAVES * 4 * a.bsp;
+        // big batches: every kind of file segment has its own kernel
+        const bool lean = (snap->n_lean != 0 || snap->n_small != 0) && !pr.force_generic && P < 0x80000000ull && qb <= 24u &&   // pair indices + a tag bit in the deferred lists; 8 spare bits in q
+                          total >= lean_min_probes(snap->ctx);
+        if (!single_fast) FPX_HIP(hipEventRecord(ws->ev_probe0, st));
+        if (pr.attempt > 0 && (snap->n_lean || snap->n_direct))
+            FPX_HIP(hipMemsetAsync(ws->d_def_count, 0, b.def_words * sizeof(unsigned int), st));   // (first attempt: k_make_keys)
+        if (snap->n_direct) {
+            // direct-addressed segments: their kernels serve every batch size -- the grouped ones through their group's
+            // directory (fpx_group.hpp: one thread per hash), the others one thread per hash and segment (fpx_direct.hpp)
+            const uint32_t n_solo = snap->n_solo;
+            const SegDesc* d_solo = snap->d_solo;
+            const uint64_t wgs_solo = (P + DK_WG * DK_KPL - 1) / (DK_WG * DK_KPL) * n_solo;
+            const uint64_t wgs_group = (P + FK_WG - 1) / FK_WG * snap->n_group;
+            // statistics: spread over 64 lines when thousands of workgroups end with them (see LEAN_STAT_SETS)
+            pr.spread = !single_fast && wgs_solo + wgs_group >= 1024;
+            unsigned long long* stat_sets = pr.spread ? device_stat_sets(b) : nullptr;
+            if (snap->n_group) {
+                ProbeArgs gk = a;
+                gk.segs = snap->d_direct; gk.lean_stats = stat_sets;
+                if (binned) { const BinArgs& h = pr.bins->h; gk.bins = h.bins; gk.bin_cap = h.bin_cap; gk.bin_count = h.bin_count; gk.bin_shift = h.shift; gk.rec32 = h.rec32; }
+                if (binned) { gk.refs = pr.bins->ref_cap ? ws->d_refs : nullptr; gk.ref_cap = pr.bins->ref_cap; }
+                gk.rounds = (uint32_t)std::max<uint64_t>(1, std::min<uint64_t>(6, wgs_group / 6000));   // (8192 x 1000: 0.626 / 0.580 / 0.566 / 0.564 ms at 2 / 3 / 4 / 6)
+                // (hot-hash data -- the previous batch brought 16+ records per key: a workgroup's rounds wait for the waves that copy the
+                // long lists; three rounds: 3.5 ms per batch of 8192 on distribution Z where five take 4.4)
+                if (fast && pr.bins->est_H > 16ull * P) gk.rounds = std::min(gk.rounds, 3u);
+                const uint64_t per_wg_gk = (uint64_t)FK_WG * gk.rounds;
+                for (const GroupDesc& gd : snap->h_group) {              // one launch per group: its descriptor is a kernel argument
+                    const GroupArgs gargs{gd, snap->d_direct};
+                    const dim3 gridg((uint32_t)((P + per_wg_gk - 1) / per_wg_gk));
+                    const Group* grp = snap->groups[&gd - snap->h_group.data()].get();
+                    launch_probe_group(grp->packed, grp->ns == 8u, binned, gk.qstats != nullptr, gridg, st, gk, gargs);
                 }
-            } else if (grp->ns == 8u) {
-                if (mem) { if (want_q) launch(k_search_query<8, true, true, false>); else launch(k_search_query<8, false, true, false>); }
-                else { if (want_q) launch(k_search_query<8, true, false, false>); else launch(k_search_query<8, false, false, false>); }
-            } else {
-                if (mem) { if (want_q) launch(k_search_query<16, true, true, false>); else launch(k_search_query<16, false, true, false>); }
-                else { if (want_q) launch(k_search_query<16, true, false, false>); else launch(k_search_query<16, false, false, false>); }
+                pr.used_fused = true;
             }
-            if (up_chunks && c + 1u < up_chunks && (rc = upload_piece(c + 1u))) return rc;       // (the next piece crosses PCIe under this kernel)
+            if (n_solo) {
+                ProbeArgs dk = a;
+                dk.segs = d_solo; dk.lean_stats = stat_sets;
+                dk.rounds = (uint32_t)std::max<uint64_t>(1, std::min<uint64_t>(4, wgs_solo / 8192));
+                const uint64_t per_wg_dk = (uint64_t)DK_WG * DK_KPL * dk.rounds;
+                hipLaunchKernelGGL(k_probe_direct, dim3((uint32_t)((P + per_wg_dk - 1) / per_wg_dk), n_solo), dim3(DK_WG), 0, st, dk);
+            }
         }
+        if (lean) {
+            if (snap->n_lean) {
+                // main kernel: k_probe_lean8 over the dense 512-B segments
+                pr.spread = true;
+                ProbeArgs l = a;
+                // rounds of 1024 pairs per workgroup: more rounds amortise the workgroup's set-up (decode tables, barriers) --
+                // measured at 8.2 M pairs x 16 segments: 5.48 ms with 1, 5.11 with 2, 5.01 with 6, 5.14 with 16 -- as long
+                // as the grid still fills the chip several times over (>= 4096 workgroups)
+                const uint64_t wgs_at_1 = (P + 1023) / 1024 * snap->n_lean;
+                l.segs = snap->d_lean; l.ctr_off = 8u;
+                l.rounds = (uint32_t)std::max<uint64_t>(1, std::min<uint64_t>(6, wgs_at_1 / 4096));
+                l.lean_stats = device_stat_sets(b);
+                const size_t lds8 = STAGE_CAP * sizeof(uint64_t) + sizeof(LeanLut) + (size_t)L8_WAVES * 8 * L8_SLOT;
+                const uint64_t per_wg_8 = (uint64_t)L8_WAVES * 64u * LEAN_KPL * l.rounds;
+                const uint32_t gx8 = (uint32_t)((P + per_wg_8 - 1) / per_wg_8);
+                // d_lean lists the segments whose blocks' head (header, hashes, docid control bytes) fits two lines first:
+                // they take the partial-fetch instantiation, the rest the whole-block one
+                if (snap->n_lean2)
+                    hipLaunchKernelGGL(k_probe_lean8<2>, dim3(gx8, snap->n_lean2), dim3(L8_WG), lds8, st, l);
+                if (snap->n_lean > snap->n_lean2) {
+                    ProbeArgs l4 = l;
+                    l4.segs = snap->d_lean + snap->n_lean2;
+                    l4.def_list = l.def_list + (size_t)snap->n_lean2 * l.def_cap;
+                    l4.def_count = l.def_count + (size_t)snap->n_lean2 * DEF_COUNT_STRIDE;
+                    hipLaunchKernelGGL(k_probe_lean8<4>, dim3(gx8, snap->n_lean - snap->n_lean2), dim3(L8_WG), lds8, st, l4);
+                }
+            }
+            FPX_HIP(hipEventRecord(ws->ev_probe1, st));
+            // auxiliary passes: the rows the lean kernel deferred, and the segments it does not suit
+            if (snap->n_lean) {
+                ProbeArgs d = a;
+                d.segs = snap->d_lean; d.ppw = 16u; d.rounds = 1u;
+                const uint64_t per_wg_d = (uint64_t)PWAVES * d.ppw;
+                // persistent workgroups striding over the device-side list: about 1024 of them over all segments
+                // ... sized from the longest list of the workspace's previous batch (x4; any grid is correct, the list is
+                // walked in strides): the usual lists hold a few dozen rows, and a grid of a thousand 512-thread
+                // workgroups that find nothing to do still costs 35 us
+                const uint64_t gxd_cap = std::max<uint64_t>(64, (1024 + snap->n_lean - 1) / snap->n_lean);
+                const uint64_t want_d = ws->hint_P ? std::max<uint64_t>(1, (4ull * ws->hint_def + per_wg_d - 1) / per_wg_d) : gxd_cap;
+                const uint32_t gxd = (uint32_t)std::min<uint64_t>(std::min<uint64_t>((b.def_cap + per_wg_d - 1) / per_wg_d, gxd_cap), want_d);
+                hipLaunchKernelGGL((k_probe<true, true>), dim3(gxd, snap->n_lean), dim3(PWG), lds, st, d);
+            }
+            if (snap->n_small) {
+                hipLaunchKernelGGL(k_probe_small, dim3((uint32_t)std::min<uint64_t>((P + (uint64_t)WG * SMALL_KPT - 1) / ((uint64_t)WG * SMALL_KPT), SMALL_GRID)), dim3(WG), 0, st,
+                                   snap->d_small, snap->n_small, keys.d_pairs, P, qb, d_hits, (uint64_t)ws->cap_hits, ws->d_counters,
+                                   b.want_q ? ws->d_qstats : (unsigned long long*)nullptr);
+            }
+            if (snap->n_gen) {
+                ProbeArgs ge = a;
+                ge.segs = snap->d_gen;
+                if (snap->gen_all_512) hipLaunchKernelGGL((k_probe<true, false>), dim3(gx, snap->n_gen), dim3(PWG), lds, st, ge);
+                else hipLaunchKernelGGL((k_probe<false, false>), dim3(gx, snap->n_gen), dim3(PWG), lds, st, ge);
+            }
+            FPX_HIP(hipEventRecord(ws->ev_probe2, st));
+            pr.used_lean = true;
+        } else {
+            a.segs = snap->d_file;
+            if (snap->n_file) {
+                if (snap->all_512) hipLaunchKernelGGL((k_probe<true, false>), dim3(gx, snap->n_file), dim3(PWG), lds, st, a);
+                else hipLaunchKernelGGL((k_probe<false, false>), dim3(gx, snap->n_file), dim3(PWG), lds, st, a);
+            }
+            if (!single_fast) FPX_HIP(hipEventRecord(ws->ev_probe1, st));
+        }
+        if (pr.spread && !fast)            // (the device-sized path publishes them at its end, with everything else)
+            FPX_HIP(hipMemcpyAsync(ws->h_def_count, ws->d_def_count, b.def_words * sizeof(unsigned int), hipMemcpyDeviceToHost, st));
         FPX_HIP(hipGetLastError());
-        FPX_HIP(hipEventRecord(ws->ev_probe1, st));
-        fpx_result* d_res = partial ? out : ws->d_out;
-        uint32_t* d_res_n = partial ? out_n : ws->d_out_n;
-        bool staged = false;
-        if (!partial && (rc = staged_targets(ws, snap->ctx, B, out_cap, &staged, &d_res_n, &d_res))) return rc;
-        hipLaunchKernelGGL(k_finish, dim3((B + 127) / 128), dim3(128), 0, st,
-                           (const uint64_t*)ws->d_cands[0], (uint64_t)0, d_opts, B, sbf, partial ? 1 : 0, d_res, out_cap, d_res_n,
-                           (const uint64_t*)d_qcand, (const uint32_t*)d_qcand_n, stats ? ws->d_counters : nullptr);
-        // (the batch's counters and statistics sets into the host's mapped copies: after the first pass, and again after a redo)
-        auto publish = [&]() -> int {
-            PublishArgs pa{};
-            pa.counters = ws->d_counters; pa.h_counters = mapped_address(ws->h_counters);
-            pa.a_src = ws->d_def_count; pa.a_dst = mapped_address(ws->h_def_count); pa.a_n = (uint32_t)def_words;
-            if (!pa.h_counters || !pa.a_dst) { set_error("page-locked host memory is not mapped into the device"); return FPX_E_DEVICE; }
-            hipLaunchKernelGGL(k_publish, dim3(4), dim3(256), 0, st, pa);
-            FPX_HIP(hipGetLastError());
-            return FPX_OK;
-        };
-        if ((rc = publish())) return rc;
-        FPX_HIP(hipEventRecord(ws->ev_end, st));
-        FPX_SYNC(ws);
-#ifdef FPX_QS_PROF
-        fprintf(stderr, "qs_prof clocks/query: setup %.0f dedup %.0f rounds %.0f tasks %.0f count+exact %.0f handover %.0f", ws->h_counters[CTR_HIST] / (double)B, ws->h_counters[CTR_HIST + 1] / (double)B,
-                ws->h_counters[CTR_HIST + 2] / (double)B, ws->h_counters[CTR_HIST + 3] / (double)B, ws->h_counters[CTR_HIST + 4] / (double)B, ws->h_counters[CTR_HIST + 5] / (double)B);
-        // (the finer marks: waits inside dedup, the rounds and before the tasks)
-        fprintf(stderr, " | dedup: hash wait %.0f | rounds: hash wait %.0f heads wait %.0f words wait %.0f probe %.0f | next offsets wait %.0f\n", ws->h_counters[CTR_HIST + 6] / (double)B,
-                ws->h_counters[CTR_HIST + 7] / (double)B, ws->h_counters[CTR_HIST + 8] / (double)B, ws->h_counters[CTR_HIST + 9] / (double)B, ws->h_counters[CTR_HIST + 10] / (double)B,
-                ws->h_counters[CTR_HIST + 11] / (double)B);
-#endif
-        if (ws->h_counters[CTR_BINFAIL] != 0 || ws->h_counters[CTR_MAXSCORE] != 0 || ws->h_counters[CTR_CANDS] > ws->cap_cands) {
-            if (ws->h_counters[CTR_BINFAIL] != 0) __atomic_store_n(&snap->qs_skip, 32u, __ATOMIC_RELAXED);
-            return FPX_REDO_QS;
-        }
-        // ---- option hot_wg: the queries whose records outgrew the LDS array were named in the redo list, with nothing counted and no
-        //      candidate; k_search_classes searches each of them once per doc class (fpx_qsearch.hpp), into the same slots and shared list.
-        //      A few of them: the batch stays here and nothing backs off.  More than qs_redo_limit(B): the pipeline and the back-off, as
-        //      before -- a walk per class costs more than the pipeline's one once much of a batch is hot, and hot traffic comes in runs.
-        //      (The shared list's length is known to the host only behind a synchronisation of its own: the sort below needs it.)
-        const uint64_t R = hot_wg ? ws->h_counters[CTR_REDO] : 0;
-        if (R != 0) {
-            if (R > qs_redo_limit(B) || R > qa.redo_cap) {
-                __atomic_store_n(&snap->qs_skip, 32u, __ATOMIC_RELAXED);
-                return FPX_REDO_QS;
-            }
-            qa.q_begin = 0u; qa.q_end = (uint32_t)R; qa.next_q = nullptr; qa.stagger = 0u;      // (entries of the list; all pieces of a chunked upload have arrived)
-            const dim3 rgrid(std::min<uint32_t>((uint32_t)R, (uint32_t)cus * QS_WGS_PER_CU));
-            auto launch = [&](auto kernel) { hipLaunchKernelGGL(kernel, rgrid, dim3(QS_WG), QS_LDS_BYTES, st, qa, gargs); };
-            if (grp->ns == 8u) { if (qa.mem_tab != nullptr) launch(k_search_classes<8, true>); else launch(k_search_classes<8, false>); }
-            else { if (qa.mem_tab != nullptr) launch(k_search_classes<16, true>); else launch(k_search_classes<16, false>); }
-            if ((rc = publish())) return rc;
-            FPX_HIP(hipEventRecord(ws->ev_end, st));
-            FPX_SYNC(ws);
-            if (ws->h_counters[CTR_BINFAIL] != 0 || ws->h_counters[CTR_MAXSCORE] != 0 || ws->h_counters[CTR_CANDS] > ws->cap_cands) {
-                if (ws->h_counters[CTR_BINFAIL] != 0) __atomic_store_n(&snap->qs_skip, 32u, __ATOMIC_RELAXED);
-                return FPX_REDO_QS;
-            }
-        }
-        uint64_t Cf = 0;
-        int ccur2 = 0;
-        if (ws->h_counters[CTR_CANDS] != 0 || R != 0) {
-            // some queries have more candidates than slots: sort the shared list and finish again (second round trip); the same
-            // second k_finish takes the redone queries' candidates from their slots
-            Cf = ws->h_counters[CTR_CANDS];
-            if (Cf != 0) {
-                const size_t tb2 = sort_u64_temp_bytes(Cf, 0, 64);
-                if ((rc = grow(reinterpret_cast<uint8_t**>(&ws->d_temp), &ws->cap_temp, tb2 + 256))) return rc;
-                FPX_HIP(sort_u64(ws->d_temp, ws->cap_temp, ws->d_cands[0], ws->d_cands[1], Cf, 0, 64, st, &ccur2));
-            }
-            if (stats) FPX_HIP(hipMemsetAsync(&ws->d_counters[CTR_SLOTCANDS], 0, sizeof(unsigned long long), st));
-            hipLaunchKernelGGL(k_finish, dim3((B + 127) / 128), dim3(128), 0, st,
-                               (const uint64_t*)ws->d_cands[ccur2], Cf, d_opts, B, sbf, partial ? 1 : 0, d_res, out_cap, d_res_n,
-                               (const uint64_t*)d_qcand, (const uint32_t*)d_qcand_n, stats ? ws->d_counters : nullptr);
-            FPX_HIP(hipGetLastError());
-            FPX_HIP(hipMemcpyAsync(&ws->h_counters[CTR_SLOTCANDS], &ws->d_counters[CTR_SLOTCANDS], sizeof(unsigned long long), hipMemcpyDeviceToHost, st));
-            FPX_HIP(hipEventRecord(ws->ev_end, st));
-            FPX_SYNC(ws);
-        }
-        if (!partial && (rc = deliver_results(ws, B, out_cap, staged, out, out_n, st))) return rc;
-        const unsigned long long* ls = reinterpret_cast<const unsigned long long*>(ws->h_def_count + def_stat_off);
-        unsigned long long blocks = 0, docs = 0, probes = 0, dreads = 0, bytes_off = 0, records = 0;
-        for (uint32_t i = 0; i < LEAN_STAT_SETS; ++i) {
-            blocks += ls[i * 8 + 1]; docs += ls[i * 8 + 2]; probes += ls[i * 8 + 3]; dreads += ls[i * 8 + 4];
-            bytes_off += ls[i * 8 + 5]; records += ls[i * 8 + 7];
-        }
-        gather_hist(ws->batch_hist, ws->h_counters, ls, probes);
-        if (stats) {
-            float ms = 0.f, total_ms = 0.f;
-            (void)hipEventElapsedTime(&ms, ws->ev_probe0, ws->ev_probe1);
-            (void)hipEventElapsedTime(&total_ms, ws->ev_begin, ws->ev_end);
-            stats->probes += probes; stats->scanned_blocks += blocks; stats->scanned_docs += docs; stats->hits += records;
-            stats->algorithmic_bytes += blocks * 512ull + bytes_off;
-            stats->candidates += Cf + ws->h_counters[CTR_SLOTCANDS];
-            stats->probe_kernel_ms += ms; stats->total_gpu_ms += total_ms; stats->probe_launches += 1;
-            stats->probe_kernel_bytes += blocks * 512ull + bytes_off;
-            stats->probe_kernel_fetched_bytes += (dreads + 1) / 2 * 128ull;
-            stats->path_flags |= 1u | (Cf ? 2u : 0u) | 4u | 64u | (qs_filt ? 256u : 0u) | (R != 0 ? 1024u : 0u);
-        }
-        if ((rc = deliver_qstats())) return rc;
-        ws->hint_P = P; ws->hint_H = std::max<uint64_t>(records, 1);          // (sizes the pipeline's bins should a later batch take it)
-        ws->hint_misc = 0; ws->hint_def = 0;
-        return FPX_OK;
+        pr.launches += 1;
     }
-    if (side_path) {
-        if ((rc = grow(&ws->d_qcand, &ws->cap_qcand, (size_t)B * QCAND_SLOTS + 2 * ((size_t)B / 2 + 1)))) return rc;
-        uint64_t* d_qcand = ws->d_qcand;
-        uint32_t* d_qcand_n = reinterpret_cast<uint32_t*>(ws->d_qcand + (size_t)B * QCAND_SLOTS);
-        const size_t cand_guess0 = std::max<size_t>(1u << 16, (size_t)B * 64);
-        if (ws->cap_cands < cand_guess0 && (rc = grow_pair(ws->d_cands, &ws->cap_cands, cand_guess0))) return rc;
-        const uint32_t sbf = 32u - qb;
-        hipLaunchKernelGGL(k_qs_zero, dim3(8), dim3(256), 0, st, ws->d_counters, ws->d_def_count, (uint32_t)def_words);
-        FPX_HIP(hipEventRecord(ws->ev_probe0, st));
-        SideArgs sa{};
-        sa.hashes_base = d_hashes_base; sa.offsets = d_offsets; sa.opts = d_opts; sa.B = B; sa.sb = sbf;
-        sa.cands = ws->d_cands[0]; sa.cand_cap = ws->cap_cands; sa.qcand = d_qcand; sa.qcand_n = d_qcand_n;
-        sa.counters = ws->d_counters; sa.stat_sets = reinterpret_cast<unsigned long long*>(ws->d_def_count + def_stat_off);
-        sa.qstats = want_q ? ws->d_qstats : nullptr; sa.cancel = cancel;
-        sa.small = snap->d_small; sa.n_small = snap->n_small; sa.solo = snap->d_solo; sa.n_solo = snap->n_solo;
-        // as many workgroups as the chip holds at once (LDS: SIDE_WGS_PER_CU per CU); each takes every gridDim.x-th query
-        static std::atomic<int> side_cus_of[64];             // (asked of the runtime once per device, as the block above does)
-        int cus = side_cus_of[(unsigned)snap->ctx->device & 63u].load(std::memory_order_relaxed);
-        if (cus == 0) {
-            if (hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, snap->ctx->device) != hipSuccess || cus <= 0) { (void)hipGetLastError(); cus = 256; }
-            side_cus_of[(unsigned)snap->ctx->device & 63u].store(cus, std::memory_order_relaxed);
-        }
-        hipLaunchKernelGGL(k_search_side, dim3(std::min<uint32_t>(B, (uint32_t)cus * SIDE_WGS_PER_CU)), dim3(SIDE_WG), SIDE_LDS_BYTES, st, sa);
+    if (P && snap->n_mem && snap->d_memtab) {
+        hipLaunchKernelGGL(k_probe_memtab, dim3(memtab_grid(P)), dim3(WG), 0, st, (const uint64_t*)snap->d_memtab, (const uint32_t*)snap->d_membucket,
+                           keys.d_pairs, P, qb, key_skip, d_hits, (uint64_t)ws->cap_hits, ws->d_counters,
+                           (const unsigned long long*)nullptr, 0ull, (const uint32_t*)snap->d_membits);
         FPX_HIP(hipGetLastError());
-        FPX_HIP(hipEventRecord(ws->ev_probe1, st));
-        fpx_result* d_res = partial ? out : ws->d_out;
-        uint32_t* d_res_n = partial ? out_n : ws->d_out_n;
-        bool staged = false;
-        if (!partial && (rc = staged_targets(ws, snap->ctx, B, out_cap, &staged, &d_res_n, &d_res))) return rc;
-        hipLaunchKernelGGL(k_finish, dim3((B + 127) / 128), dim3(128), 0, st,
-                           (const uint64_t*)ws->d_cands[0], (uint64_t)0, d_opts, B, sbf, partial ? 1 : 0, d_res, out_cap, d_res_n,
-                           (const uint64_t*)d_qcand, (const uint32_t*)d_qcand_n, stats ? ws->d_counters : nullptr);
-        {
-            PublishArgs pa{};
-            pa.counters = ws->d_counters; pa.h_counters = mapped_address(ws->h_counters);
-            pa.a_src = ws->d_def_count; pa.a_dst = mapped_address(ws->h_def_count); pa.a_n = (uint32_t)def_words;
-            if (!pa.h_counters || !pa.a_dst) { set_error("page-locked host memory is not mapped into the device"); return FPX_E_DEVICE; }
-            hipLaunchKernelGGL(k_publish, dim3(4), dim3(256), 0, st, pa);
-            FPX_HIP(hipGetLastError());
-        }
-        FPX_HIP(hipEventRecord(ws->ev_end, st));
-        FPX_SYNC(ws);
-        if (ws->h_counters[CTR_BINFAIL] != 0 || ws->h_counters[CTR_MAXSCORE] != 0 || ws->h_counters[CTR_CANDS] > ws->cap_cands) {
-            if (ws->h_counters[CTR_BINFAIL] != 0) __atomic_store_n(&snap->qs_skip, 32u, __ATOMIC_RELAXED);
-            return FPX_REDO_QS;                           // (that snapshot or part alone: run_with_redos)
-        }
-        uint64_t Cf = 0;
-        int ccur2 = 0;
-        if (ws->h_counters[CTR_CANDS] != 0) {
-            // some queries have more candidates than slots: sort the shared list and finish again (second round trip)
-            Cf = ws->h_counters[CTR_CANDS];
-            const size_t tb2 = sort_u64_temp_bytes(Cf, 0, 64);
-            if ((rc = grow(reinterpret_cast<uint8_t**>(&ws->d_temp), &ws->cap_temp, tb2 + 256))) return rc;
-            FPX_HIP(sort_u64(ws->d_temp, ws->cap_temp, ws->d_cands[0], ws->d_cands[1], Cf, 0, 64, st, &ccur2));
-            if (stats) FPX_HIP(hipMemsetAsync(&ws->d_counters[CTR_SLOTCANDS], 0, sizeof(unsigned long long), st));
-            hipLaunchKernelGGL(k_finish, dim3((B + 127) / 128), dim3(128), 0, st,
-                               (const uint64_t*)ws->d_cands[ccur2], Cf, d_opts, B, sbf, partial ? 1 : 0, d_res, out_cap, d_res_n,
-                               (const uint64_t*)d_qcand, (const uint32_t*)d_qcand_n, stats ? ws->d_counters : nullptr);
-            FPX_HIP(hipGetLastError());
-            FPX_HIP(hipMemcpyAsync(&ws->h_counters[CTR_SLOTCANDS], &ws->d_counters[CTR_SLOTCANDS], sizeof(unsigned long long), hipMemcpyDeviceToHost, st));
-            FPX_HIP(hipEventRecord(ws->ev_end, st));
-            FPX_SYNC(ws);
-        }
-        if (!partial && (rc = deliver_results(ws, B, out_cap, staged, out, out_n, st))) return rc;
-        const unsigned long long* ls = reinterpret_cast<const unsigned long long*>(ws->h_def_count + def_stat_off);
-        unsigned long long blocks = 0, docs = 0, probes = 0, dreads = 0, bytes_off = 0, records = 0;
-        for (uint32_t i = 0; i < LEAN_STAT_SETS; ++i) {
-            blocks += ls[i * 8 + 1]; docs += ls[i * 8 + 2]; probes += ls[i * 8 + 3]; dreads += ls[i * 8 + 4];
-            bytes_off += ls[i * 8 + 5]; records += ls[i * 8 + 7];
-        }
-        gather_hist(ws->batch_hist, ws->h_counters, ls, probes);
-        if (stats) {
-            float ms = 0.f, total_ms = 0.f;
-            (void)hipEventElapsedTime(&ms, ws->ev_probe0, ws->ev_probe1);
-            (void)hipEventElapsedTime(&total_ms, ws->ev_begin, ws->ev_end);
-            stats->probes += probes; stats->scanned_blocks += blocks; stats->scanned_docs += docs; stats->hits += records;
-            stats->algorithmic_bytes += blocks * 512ull + bytes_off;
-            stats->candidates += Cf + ws->h_counters[CTR_SLOTCANDS];
-            stats->probe_kernel_ms += ms; stats->total_gpu_ms += total_ms; stats->probe_launches += 1;
-            stats->probe_kernel_bytes += blocks * 512ull + bytes_off;
-            stats->probe_kernel_fetched_bytes += (dreads + 1) / 2 * 128ull;
-            stats->path_flags |= 1u | (Cf ? 2u : 0u) | 512u;
-        }
-        if ((rc = deliver_qstats())) return rc;
-        ws->hint_P = P; ws->hint_H = std::max<uint64_t>(records, 1);          // (sizes the pipeline's bins should a later batch take it)
-        ws->hint_misc = 0; ws->hint_def = 0;
-        return FPX_OK;
     }
-    // ---- 3+4: probes (rerun with a larger hit buffer on overflow)
-    uint64_t H = 0;
-    float probe_ms = 0.f, aux_ms = 0.f;
-    uint32_t probe_launches = 0;
-    if (ws->cap_hits == 0) {
-        size_t want = std::max<size_t>(1u << 20, (size_t)P * std::max<uint32_t>(1u, snap->n_file + snap->n_direct + snap->n_mem));
-        if ((rc = grow_pair(ws->d_hits, &ws->cap_hits, want))) return rc;
-    }
-    // ---- the device-sized path (fpx_partition.hpp): the hit records are binned by query as they are produced, every size
-    //      downstream is read from device memory, and the batch needs ONE host round trip (two when queries overflow their
-    //      candidate slots) instead of three.  It needs an estimate of the record count to size its bins: the first batch of a
-    //      workspace takes the general path.  Anything it cannot handle (a full bin, a full deferred list, scores too wide
-    //      for the candidate key) is noticed after the synchronisation and the batch is redone on the general path.
-    const bool fast_enabled = ctx_opt(snap->ctx, OPT_FAST) != 0;
-    const uint32_t nb_bits = qb > BIN_QUERIES_LOG2 ? qb - BIN_QUERIES_LOG2 : 0u;
-    bool fast = fast_enabled && !ex && !no_fast && !single_fast && B >= 2u && P != 0 && qb <= 24u && (1u << nb_bits) <= MAX_BINS &&
-                ws->hint_H != 0 && ws->hint_P != 0;
-    if (fast && ws->fast_penalty != 0) { ws->fast_penalty -= 1; fast = false; }
-    BinArgs h_bin{};
-    constexpr uint32_t HOT_REF_CAP = 4096;                                       // references to hot lists a bin takes (16 bytes each)
-    uint32_t ref_cap = 0;                                                        // 0: hot lists are copied into the bins
-    uint32_t* d_bin_count = nullptr;
-    uint32_t* d_qcount = nullptr;
-    uint64_t est_H = 0;
-    constexpr size_t BINQ_HEAD = 64 / sizeof(uint32_t);                          // room for the BinArgs the kernels read
+    return FPX_OK;
+}
+
+// ---- the device-sized path (fpx_partition.hpp): the hit records are binned by query as they are produced, every size downstream is read
+//      from device memory, and the batch needs ONE host round trip (two when queries overflow their candidate slots) instead of three.
+//      It needs an estimate of the record count to size its bins: the first batch of a workspace takes the general path.  Anything it
+//      cannot handle (a full bin, a full deferred list, scores too wide for the candidate key) is noticed after the synchronisation and
+//      the batch is redone on the general path (FPX_REDO).
+constexpr uint32_t HOT_REF_CAP = 4096;                                       // references to hot lists a bin takes (16 bytes each)
+static uint32_t level1_bits(unsigned qb) { return qb > BIN_QUERIES_LOG2 ? qb - BIN_QUERIES_LOG2 : 0u; }
+
+// the bins' form, sizes and buffers; their counts zeroed on the stream
+static int size_bins(Batch& b, const Keys& keys, Bins* bins)
+{
+    Snapshot* snap = b.snap; Workspace* ws = b.ws; const uint32_t B = b.B; const uint64_t P = b.P; int rc;
+    BinArgs& h_bin = bins->h;
     // ... and its short form when the records come from groups of direct-addressed segments alone: k_probe_group drops them
     // into bins of 2^BQ queries itself and k_score_bin scores a bin per workgroup (fpx_score_bin.hpp) -- no partition kernels
     // Queries per bin: eight, fewer for batches that would not give k_score_bin ~2048 workgroups otherwise (a workgroup's time is
     // a chain of tile-load latencies: 8192 queries in bins of 4: 170 -> 154 us, 1024 queries in bins of 2: 66 -> 29 us)
     uint32_t bin_q_log2 = 3u;
     while (bin_q_log2 > 1u && (B >> bin_q_log2) < 2048u) --bin_q_log2;
-    const bool binned_enabled = ctx_opt(snap->ctx, OPT_BINNED) != 0;
-    bool binned = false;
     uint32_t sbins = 0;
     // (segments direct-addressed on their own and memory segments append their records to the misc buffer, which k_bin bins: the
     // snapshot a live index has between merges keeps the one-launch scoring of its groups)
-    if (fast && binned_enabled && flagged && snap->n_group != 0 && bin_q_log2 >= 1u && bin_q_log2 <= 4u) {
-        uint32_t floor_lo = 0xFFFFFFFFu;
-        for (uint32_t q = 0; q < B; ++q) {
-            const uint64_t raw_len = offsets[q + 1] - offsets[q];
-            floor_lo = std::min(floor_lo, opts[q].has_min_score ? opts[q].min_score : (uint32_t)((raw_len + 19) / 20));
-        }
+    if (ctx_opt(snap->ctx, OPT_BINNED) != 0 && keys.flagged && snap->n_group != 0 && bin_q_log2 >= 1u && bin_q_log2 <= 4u) {
         sbins = (B + (1u << bin_q_log2) - 1u) >> bin_q_log2;
         // (a floor of 1 or 2 -- the legacy protocol's -- makes every counted doc a candidate: k_score's count-only round, which
         // raises the floor to top * pct / 100 before anything is emitted, handles those)
-        binned = floor_lo > 2u && sbins <= MAX_SBINS;
-        if (!binned) sbins = 0;            // (the two-level partition's layout below: its counts must sit where its memset zeroes them)
+        bins->binned = min_floor(b.offsets, b.opts, B) > 2u && sbins <= MAX_SBINS;
+        if (!bins->binned) sbins = 0;            // (the two-level partition's layout below: its counts must sit where its memset zeroes them)
     }
-    if (fast) {
-        est_H = (uint64_t)((double)ws->hint_H * (double)P / (double)ws->hint_P) + 1024;
-        const size_t want = (size_t)(2 * est_H + (1u << 16)) + (binned ? (size_t)sbins * 8192u : 0u);      // bins get 2x their expected fill
-        if (ws->cap_hits < want && (rc = grow_pair(ws->d_hits, &ws->cap_hits, want))) return rc;
-        const size_t words = BINQ_HEAD + (size_t)std::max<uint32_t>(MAX_BINS, sbins) * BIN_STRIDE + (size_t)B + 64 + sbins;
-        if (words > ws->cap_binq) {
-            if (ws->d_binq) (void)hipFree(ws->d_binq);
-            if (ws->d_qcursor) (void)hipFree(ws->d_qcursor);
-            ws->d_binq = nullptr; ws->d_qcursor = nullptr; ws->cap_binq = 0;
-            const size_t ncap = words * 5 / 4;
-            FPX_HIP(dmalloc(&ws->d_binq, ncap * sizeof(uint32_t)));
-            FPX_HIP(dmalloc(&ws->d_qcursor, ncap * sizeof(unsigned long long)));
-            ws->cap_binq = ncap;
-        }
-        if (!ws->h_bins) FPX_HIP(hipHostMalloc(reinterpret_cast<void**>(&ws->h_bins), (BINQ_HEAD + (size_t)MAX_BINS * BIN_STRIDE + MAX_SBINS) * sizeof(uint32_t), hipHostMallocMapped));
-        d_bin_count = ws->d_binq + BINQ_HEAD;
-        d_qcount = d_bin_count + (size_t)std::max<uint32_t>(MAX_BINS, sbins) * BIN_STRIDE;
-        h_bin.bins = ws->d_hits[0];
-        h_bin.bin_count = d_bin_count;
-        if (binned) {
-            // 4-byte records where the doc ids leave room for the query's bits inside its bin (fpx_partition.hpp)
-            const bool rec32_enabled = ctx_opt(snap->ctx, OPT_REC32) != 0;
-            h_bin.rec32 = rec32_enabled && !__atomic_load_n(&snap->rec32_refused, __ATOMIC_RELAXED) &&
-                          snap->max_doc_declared < (0xFFFFFFFFu >> bin_q_log2) ? 1u : 0u;
-            h_bin.counters = ws->d_counters;
-            h_bin.nbins = sbins; h_bin.shift = bin_q_log2;
-            // twice the expected share + room for the spread of a small bin; a bin that overflows is seen after the batch's
-            // synchronisation and the batch is redone on the general path
-            h_bin.bin_cap = std::min<uint64_t>(ws->cap_hits / sbins, std::max<uint64_t>(2 * est_H / sbins + 8192, 16384)) & ~(uint64_t)31;      // (whole lines per bin: reservations padded to BIN_ALIGN records start on a sector)
-            FPX_HIP(hipMemsetAsync(d_bin_count, 0, (size_t)sbins * BIN_STRIDE * sizeof(uint32_t), st));
-            // Hot-hash data (the last batch brought 16+ records per key): the lists of a hot hash -- thousands of docs, the same for every
-            // query that holds the hash -- reach the score kernel BY REFERENCE (ProbeArgs::refs): HOT_REF_CAP entries per bin, their
-            // counts in the bins' counter lines (zeroed above); a bin with more lists has the rest copied as before
-            const int64_t hot_refs = ctx_opt(snap->ctx, OPT_HOT_REFS);
-            if (hot_refs > 0 || (hot_refs < 0 && est_H > 16ull * P)) {
-                ref_cap = HOT_REF_CAP;
-                if ((size_t)sbins * ref_cap > ws->cap_refs) {
-                    if (ws->d_refs) (void)hipFree(ws->d_refs);
-                    ws->d_refs = nullptr; ws->cap_refs = 0;
-                    if (dmalloc(&ws->d_refs, (size_t)sbins * ref_cap * sizeof(uint4)) == hipSuccess) ws->cap_refs = (size_t)sbins * ref_cap;
-                    else { (void)hipGetLastError(); ref_cap = 0; }              // (no room: the lists are copied)
-                }
-            }
-        } else {
-            h_bin.nbins = 1u << nb_bits; h_bin.shift = qb - nb_bits;
-            // a bin holds at most 4x its expected share (never more than its slice of the buffer): the level-2 grids are sized by
-            // this capacity, and a workspace that has seen a huge batch must not launch that batch's grids for a small one
-            h_bin.bin_cap = std::min<uint64_t>(ws->cap_hits / h_bin.nbins, std::max<uint64_t>(4 * est_H / h_bin.nbins, 1u << 16));
-            FPX_HIP(hipMemsetAsync(d_bin_count, 0, ((size_t)MAX_BINS * BIN_STRIDE + B) * sizeof(uint32_t), st));
-        }
+    bins->sbins = sbins;
+    const uint64_t est_H = bins->est_H = (uint64_t)((double)ws->hint_H * (double)P / (double)ws->hint_P) + 1024;
+    const size_t want = (size_t)(2 * est_H + (1u << 16)) + (bins->binned ? (size_t)sbins * 8192u : 0u);      // bins get 2x their expected fill
+    if (ws->cap_hits < want && (rc = grow_pair(ws->d_hits, &ws->cap_hits, want))) return rc;
+    const size_t words = BINQ_HEAD + (size_t)std::max<uint32_t>(MAX_BINS, sbins) * BIN_STRIDE + (size_t)B + 64 + sbins;
+    if (words > ws->cap_binq) {
+        if (ws->d_binq) (void)hipFree(ws->d_binq);
+        if (ws->d_qcursor) (void)hipFree(ws->d_qcursor);
+        ws->d_binq = nullptr; ws->d_qcursor = nullptr; ws->cap_binq = 0;
+        const size_t ncap = words * 5 / 4;
+        FPX_HIP(dmalloc(&ws->d_binq, ncap * sizeof(uint32_t)));
+        FPX_HIP(dmalloc(&ws->d_qcursor, ncap * sizeof(unsigned long long)));
+        ws->cap_binq = ncap;
     }
-    bool force_generic = false, used_lean = false, spread = false, used_fused = false;
-    for (int attempt = 0;; ++attempt) {
-        used_lean = false; spread = false;
-        if (!single_fast) FPX_HIP(hipMemsetAsync(ws->d_counters, 0, CTR_COUNT * sizeof(unsigned long long), st));   // (k_make_keys did it)
-        if (want_q) FPX_HIP(hipMemsetAsync(ws->d_qstats, 0, (size_t)B * sizeof(unsigned long long), st));
-        if (P && (snap->n_file || snap->n_direct)) {
-            ProbeArgs a;
-            a.pairs = d_pairs; a.P = P; a.qb = qb;
-            // enough workgroups to fill 256 CUs; long per-wave runs amortise the index walk for big batches
-            const uint64_t total = P * snap->n_file;
-            // (16 pairs per wave also for tiny batches: a single query is bound by per-workgroup set-up, not by parallelism)
-            a.ppw = total >= (1ull << 22) ? 64u : 16u;
-            a.rounds = total >= (1ull << 25) ? 2u : 1u;
-            a.bsp = ((snap->max_block_size + 15u) & ~15u) + 32u;
-            a.hits = ws->d_hits[fast ? 1 : 0]; a.hit_cap = ws->cap_hits; a.counters = ws->d_counters;    // (fast: binned into d_hits[0] afterwards)
-            a.def_list = ws->d_def_list; a.def_count = ws->d_def_count; a.def_cap = (uint32_t)def_cap; a.ctr_off = 0; a.lean_stats = nullptr; a.cancel = cancel;
-            a.key_skip = flagged ? KEY_SKIP_FLAGGED : key_skip;
-            a.qstats = want_q ? ws->d_qstats : nullptr;
-            const uint64_t per_wg = (uint64_t)PWAVES * a.ppw * a.rounds;
-            const uint32_t gx = (uint32_t)((P + per_wg - 1) / per_wg);
-            const size_t lds = STAGE_CAP * sizeof(uint64_t) + sizeof(DecodeLut) + (size_t)PWAVES * 4 * a.bsp;
-            // big batches: every kind of file segment has its own kernel
-            const bool lean = (snap->n_lean != 0 || snap->n_small != 0) && !force_generic && P < 0x80000000ull && qb <= 24u &&   // pair indices + a tag bit in the deferred lists; 8 spare bits in q
-                              total >= lean_min_probes(snap->ctx);
-            if (!single_fast) FPX_HIP(hipEventRecord(ws->ev_probe0, st));
-            if (attempt > 0 && (snap->n_lean || snap->n_direct))
-                FPX_HIP(hipMemsetAsync(ws->d_def_count, 0, def_words * sizeof(unsigned int), st));   // (first attempt: k_make_keys)
-            if (snap->n_direct) {
-                // direct-addressed segments: their kernels serve every batch size -- the grouped ones through their group's
-                // directory (fpx_group.hpp: one thread per hash), the others one thread per hash and segment (fpx_direct.hpp)
-                const uint32_t n_solo = snap->n_solo;
-                const SegDesc* d_solo = snap->d_solo;
-                const uint64_t wgs_solo = (P + DK_WG * DK_KPL - 1) / (DK_WG * DK_KPL) * n_solo;
-                const uint64_t wgs_group = (P + FK_WG - 1) / FK_WG * snap->n_group;
-                // statistics: spread over 64 lines when thousands of workgroups end with them (see LEAN_STAT_SETS)
-                spread = !single_fast && wgs_solo + wgs_group >= 1024;
-                unsigned long long* stat_sets = spread ? reinterpret_cast<unsigned long long*>(ws->d_def_count + def_stat_off) : nullptr;
-                if (snap->n_group) {
-                    ProbeArgs gk = a;
-                    gk.segs = snap->d_direct; gk.lean_stats = stat_sets;
-                    if (binned) { gk.bins = h_bin.bins; gk.bin_cap = h_bin.bin_cap; gk.bin_count = h_bin.bin_count; gk.bin_shift = h_bin.shift; gk.rec32 = h_bin.rec32; gk.refs = ref_cap ? ws->d_refs : nullptr; gk.ref_cap = ref_cap; }
-                    gk.rounds = (uint32_t)std::max<uint64_t>(1, std::min<uint64_t>(6, wgs_group / 6000));   // (8192 x 1000: 0.626 / 0.580 / 0.566 / 0.564 ms at 2 / 3 / 4 / 6)
-                    // (hot-hash data -- the previous batch brought 16+ records per key: a workgroup's rounds wait for the waves that copy the
-                    // long lists; three rounds: 3.5 ms per batch of 8192 on distribution Z where five take 4.4)
-                    if (fast && est_H > 16ull * P) gk.rounds = std::min(gk.rounds, 3u);
-                    const uint64_t per_wg_gk = (uint64_t)FK_WG * gk.rounds;
-                    for (const GroupDesc& gd : snap->h_group) {              // one launch per group: its descriptor is a kernel argument
-                        const GroupArgs gargs{gd, snap->d_direct};
-                        const dim3 gridg((uint32_t)((P + per_wg_gk - 1) / per_wg_gk));
-                        const Group* grp = snap->groups[&gd - snap->h_group.data()].get();
-                        launch_probe_group(grp->packed, grp->ns == 8u, binned, gk.qstats != nullptr, gridg, st, gk, gargs);
-                    }
-                    used_fused = true;
-                }
-                if (n_solo) {
-                    ProbeArgs dk = a;
-                    dk.segs = d_solo; dk.lean_stats = stat_sets;
-                    const uint32_t direct_rounds = 0u;
-                    dk.rounds = direct_rounds ? direct_rounds : (uint32_t)std::max<uint64_t>(1, std::min<uint64_t>(4, wgs_solo / 8192));
-                    const uint64_t per_wg_dk = (uint64_t)DK_WG * DK_KPL * dk.rounds;
-                    hipLaunchKernelGGL(k_probe_direct, dim3((uint32_t)((P + per_wg_dk - 1) / per_wg_dk), n_solo), dim3(DK_WG), 0, st, dk);
-                }
-            }
-            if (lean) {
-                if (snap->n_lean) {
-                    // main kernel: k_probe_lean8 over the dense 512-B segments
-                    spread = true;
-                    ProbeArgs l = a;
-                    // rounds of 1024 pairs per workgroup: more rounds amortise the workgroup's set-up (decode tables, barriers) --
-                    // measured at 8.2 M pairs x 16 segments: 5.48 ms with 1, 5.11 with 2, 5.01 with 6, 5.14 with 16 -- as long
-                    // as the grid still fills the chip several times over (>= 4096 workgroups)
-                    const uint32_t lean_rounds = 0u;
-                    const uint64_t wgs_at_1 = (P + 1023) / 1024 * snap->n_lean;
-                    l.segs = snap->d_lean; l.ctr_off = 8u;
-                    l.rounds = lean_rounds ? lean_rounds : (uint32_t)std::max<uint64_t>(1, std::min<uint64_t>(6, wgs_at_1 / 4096));
-                    l.lean_stats = reinterpret_cast<unsigned long long*>(ws->d_def_count + def_stat_off);
-                    const size_t lds8 = STAGE_CAP * sizeof(uint64_t) + sizeof(LeanLut) + (size_t)L8_WAVES * 8 * L8_SLOT;
-                    const uint64_t per_wg_8 = (uint64_t)L8_WAVES * 64u * LEAN_KPL * l.rounds;
-                    const uint32_t gx8 = (uint32_t)((P + per_wg_8 - 1) / per_wg_8);
-                    // d_lean lists the segments whose blocks' head (header, hashes, docid control bytes) fits two lines first:
-                    // they take the partial-fetch instantiation, the rest the whole-block one
-                    if (snap->n_lean2)
-                        hipLaunchKernelGGL(k_probe_lean8<2>, dim3(gx8, snap->n_lean2), dim3(L8_WG), lds8, st, l);
-                    if (snap->n_lean > snap->n_lean2) {
-                        ProbeArgs l4 = l;
-                        l4.segs = snap->d_lean + snap->n_lean2;
-                        l4.def_list = l.def_list + (size_t)snap->n_lean2 * l.def_cap;
-                        l4.def_count = l.def_count + (size_t)snap->n_lean2 * DEF_COUNT_STRIDE;
-                        hipLaunchKernelGGL(k_probe_lean8<4>, dim3(gx8, snap->n_lean - snap->n_lean2), dim3(L8_WG), lds8, st, l4);
-                    }
-                }
-                FPX_HIP(hipEventRecord(ws->ev_probe1, st));
-                // auxiliary passes: the rows the lean kernel deferred, and the segments it does not suit
-                if (snap->n_lean) {
-                    ProbeArgs d = a;
-                    d.segs = snap->d_lean; d.ppw = 16u; d.rounds = 1u;
-                    const uint64_t per_wg_d = (uint64_t)PWAVES * d.ppw;
-                    // persistent workgroups striding over the device-side list: about 1024 of them over all segments
-                    // ... sized from the longest list of the workspace's previous batch (x4; any grid is correct, the list is
-                    // walked in strides): the usual lists hold a few dozen rows, and a grid of a thousand 512-thread
-                    // workgroups that find nothing to do still costs 35 us
-                    const uint64_t gxd_cap = std::max<uint64_t>(64, (1024 + snap->n_lean - 1) / snap->n_lean);
-                    const uint64_t want_d = ws->hint_P ? std::max<uint64_t>(1, (4ull * ws->hint_def + per_wg_d - 1) / per_wg_d) : gxd_cap;
-                    const uint32_t gxd = (uint32_t)std::min<uint64_t>(std::min<uint64_t>((def_cap + per_wg_d - 1) / per_wg_d, gxd_cap), want_d);
-                    hipLaunchKernelGGL((k_probe<true, true>), dim3(gxd, snap->n_lean), dim3(PWG), lds, st, d);
-                }
-                if (snap->n_small) {
-                    hipLaunchKernelGGL(k_probe_small, dim3((uint32_t)std::min<uint64_t>((P + (uint64_t)WG * SMALL_KPT - 1) / ((uint64_t)WG * SMALL_KPT), SMALL_GRID)), dim3(WG), 0, st,
-                                       snap->d_small, snap->n_small, d_pairs, P, qb, ws->d_hits[fast ? 1 : 0], (uint64_t)ws->cap_hits, ws->d_counters,
-                                       want_q ? ws->d_qstats : (unsigned long long*)nullptr);
-                }
-                if (snap->n_gen) {
-                    ProbeArgs ge = a;
-                    ge.segs = snap->d_gen;
-                    if (snap->gen_all_512) hipLaunchKernelGGL((k_probe<true, false>), dim3(gx, snap->n_gen), dim3(PWG), lds, st, ge);
-                    else hipLaunchKernelGGL((k_probe<false, false>), dim3(gx, snap->n_gen), dim3(PWG), lds, st, ge);
-                }
-                FPX_HIP(hipEventRecord(ws->ev_probe2, st));
-                used_lean = true;
-            } else {
-                a.segs = snap->d_file;
-                if (snap->n_file) {
-                    if (snap->all_512) hipLaunchKernelGGL((k_probe<true, false>), dim3(gx, snap->n_file), dim3(PWG), lds, st, a);
-                    else hipLaunchKernelGGL((k_probe<false, false>), dim3(gx, snap->n_file), dim3(PWG), lds, st, a);
-                }
-                if (!single_fast) FPX_HIP(hipEventRecord(ws->ev_probe1, st));
-            }
-            if (spread && !fast)            // (the device-sized path publishes them at its end, with everything else)
-                FPX_HIP(hipMemcpyAsync(ws->h_def_count, ws->d_def_count, def_words * sizeof(unsigned int), hipMemcpyDeviceToHost, st));
-            FPX_HIP(hipGetLastError());
-            probe_launches += 1;
-        }
-        if (P && snap->n_mem && snap->d_memtab) {
-            hipLaunchKernelGGL(k_probe_memtab, dim3(memtab_grid(P)), dim3(WG), 0, st, (const uint64_t*)snap->d_memtab, (const uint32_t*)snap->d_membucket,
-                               d_pairs, P, qb, flagged ? KEY_SKIP_FLAGGED : key_skip, ws->d_hits[fast ? 1 : 0], (uint64_t)ws->cap_hits, ws->d_counters,
-                               (const unsigned long long*)nullptr, 0ull, (const uint32_t*)snap->d_membits);
-            FPX_HIP(hipGetLastError());
-        }
-        if (single_fast || fast) break;             // nothing below needs the counts on the host yet
-        FPX_HIP(hipMemcpyAsync(ws->h_counters, ws->d_counters, CTR_COUNT * sizeof(unsigned long long), hipMemcpyDeviceToHost, st));
-        FPX_SYNC(ws);
-        if (spread) {
-            // the lean / direct kernels' statistics: LEAN_STAT_SETS copies on separate cache lines (a workgroup adds to set
-            // blockIdx.x % LEAN_STAT_SETS), summed here into the slots the code below reads
-            const unsigned long long* ls = reinterpret_cast<const unsigned long long*>(ws->h_def_count + def_stat_off);
-            unsigned long long reads = 0, blocks = 0, docs = 0, probes = 0, dreads = 0, bytes_off = 0;
-            for (uint32_t i = 0; i < LEAN_STAT_SETS; ++i) {
-                reads += ls[i * 8 + 0]; blocks += ls[i * 8 + 1]; docs += ls[i * 8 + 2]; probes += ls[i * 8 + 3]; dreads += ls[i * 8 + 4];
-                bytes_off += ls[i * 8 + 5];          // (block sizes other than 512 in the direct-addressed forms: the difference, mod 2^64)
-            }
-            ws->h_counters[CTR_LEAN_READS] = reads + (dreads + 1) / 2;           // (k_probe_direct counts 64-byte requests)
-            ws->h_counters[8 + CTR_BLOCKS] = blocks; ws->h_counters[8 + CTR_BYTES] = blocks * 512ull + bytes_off;
-            ws->h_counters[8 + CTR_DOCS] = docs; ws->h_counters[8 + CTR_PROBES] = probes;
-        }
-        if (P && (snap->n_file || snap->n_direct)) {
-            float ms = 0.f;
-            FPX_HIP(hipEventElapsedTime(&ms, ws->ev_probe0, ws->ev_probe1));
-            probe_ms = ms;
-            aux_ms = 0.f;
-            if (used_lean) FPX_HIP(hipEventElapsedTime(&aux_ms, ws->ev_probe1, ws->ev_probe2));
-        }
-        H = ws->h_counters[CTR_HITS];
-        if (used_lean) {
-            bool overflow = false;
-            for (uint32_t i = 0; i < snap->n_lean; ++i) overflow = overflow || ws->h_def_count[(size_t)i * DEF_COUNT_STRIDE] > def_cap;
-            if (overflow) {                 // pathological data: nearly every probe needs the generic path
-                if (attempt >= 3) { set_error("deferred list overflow persists"); return FPX_E_DEVICE; }
-                force_generic = true;
-                continue;
+    if (!ws->h_bins) FPX_HIP(hipHostMalloc(reinterpret_cast<void**>(&ws->h_bins), (BINQ_HEAD + (size_t)MAX_BINS * BIN_STRIDE + MAX_SBINS) * sizeof(uint32_t), hipHostMallocMapped));
+    uint32_t* d_bin_count = bins->d_bin_count = ws->d_binq + BINQ_HEAD;
+    bins->d_qcount = d_bin_count + (size_t)std::max<uint32_t>(MAX_BINS, sbins) * BIN_STRIDE;
+    h_bin.bins = ws->d_hits[0];
+    h_bin.bin_count = d_bin_count;
+    if (bins->binned) {
+        // 4-byte records where the doc ids leave room for the query's bits inside its bin (fpx_partition.hpp)
+        const bool rec32_enabled = ctx_opt(snap->ctx, OPT_REC32) != 0;
+        h_bin.rec32 = rec32_enabled && !__atomic_load_n(&snap->rec32_refused, __ATOMIC_RELAXED) &&
+                      snap->max_doc_declared < (0xFFFFFFFFu >> bin_q_log2) ? 1u : 0u;
+        h_bin.counters = ws->d_counters;
+        h_bin.nbins = sbins; h_bin.shift = bin_q_log2;
+        // twice the expected share + room for the spread of a small bin; a bin that overflows is seen after the batch's
+        // synchronisation and the batch is redone on the general path
+        h_bin.bin_cap = std::min<uint64_t>(ws->cap_hits / sbins, std::max<uint64_t>(2 * est_H / sbins + 8192, 16384)) & ~(uint64_t)31;      // (whole lines per bin: reservations padded to BIN_ALIGN records start on a sector)
+        FPX_HIP(hipMemsetAsync(d_bin_count, 0, (size_t)sbins * BIN_STRIDE * sizeof(uint32_t), b.st));
+        // Hot-hash data (the last batch brought 16+ records per key): the lists of a hot hash -- thousands of docs, the same for every
+        // query that holds the hash -- reach the score kernel BY REFERENCE (ProbeArgs::refs): HOT_REF_CAP entries per bin, their
+        // counts in the bins' counter lines (zeroed above); a bin with more lists has the rest copied as before
+        const int64_t hot_refs = ctx_opt(snap->ctx, OPT_HOT_REFS);
+        if (hot_refs > 0 || (hot_refs < 0 && est_H > 16ull * P)) {
+            bins->ref_cap = HOT_REF_CAP;
+            if ((size_t)sbins * HOT_REF_CAP > ws->cap_refs) {
+                if (ws->d_refs) (void)hipFree(ws->d_refs);
+                ws->d_refs = nullptr; ws->cap_refs = 0;
+                if (dmalloc(&ws->d_refs, (size_t)sbins * HOT_REF_CAP * sizeof(uint4)) == hipSuccess) ws->cap_refs = (size_t)sbins * HOT_REF_CAP;
+                else { (void)hipGetLastError(); bins->ref_cap = 0; }              // (no room: the lists are copied)
             }
         }
-        if (H <= ws->cap_hits) break;
-        if (attempt >= 4) { set_error("hit buffer overflow persists (%llu records)", (unsigned long long)H); return FPX_E_DEVICE; }
-        if ((rc = grow_pair(ws->d_hits, &ws->cap_hits, (size_t)H + 1024))) return rc;
+    } else {
+        const uint32_t nb_bits = level1_bits(b.qb);
+        h_bin.nbins = 1u << nb_bits; h_bin.shift = b.qb - nb_bits;
+        // a bin holds at most 4x its expected share (never more than its slice of the buffer): the level-2 grids are sized by
+        // this capacity, and a workspace that has seen a huge batch must not launch that batch's grids for a small one
+        h_bin.bin_cap = std::min<uint64_t>(ws->cap_hits / h_bin.nbins, std::max<uint64_t>(4 * est_H / h_bin.nbins, 1u << 16));
+        FPX_HIP(hipMemsetAsync(d_bin_count, 0, ((size_t)MAX_BINS * BIN_STRIDE + B) * sizeof(uint32_t), b.st));
     }
-    if (fast) {
-        // ---- 5': bins -> per-query ranges (level 2 of fpx_partition.hpp), count, finish; sizes stay on the device
-        const uint32_t tiles = (uint32_t)std::min<uint64_t>((h_bin.bin_cap + L2_TILE - 1) / L2_TILE, 0x7FFFFFFFull / 256u);
-        // (binned: only what k_probe_group could not place itself is in the misc buffer -- normally nothing; the lists of hot hashes,
-        // which go there whole, on skewed data: the grid follows what the workspace's last batch left there)
-        const uint32_t bin_grid = binned ? (uint32_t)std::min<uint64_t>(std::max<uint64_t>(64, (2 * ws->hint_misc + BIN_TILE - 1) / BIN_TILE), 8192u)
-                                         : (uint32_t)std::min<uint64_t>((2 * est_H + BIN_TILE - 1) / BIN_TILE, 8192u);
-        hipLaunchKernelGGL(k_bin, dim3(std::max(1u, bin_grid)), dim3(256), 0, st, h_bin, (const uint64_t*)ws->d_hits[1],
-                           (const unsigned long long*)&ws->d_counters[CTR_HITS], (uint64_t)ws->cap_hits);
-        if ((rc = grow(&ws->d_qrange, &ws->cap_qrange, (size_t)B * 2 + 2))) return rc;
-        if ((rc = grow(&ws->d_qcand, &ws->cap_qcand, (size_t)B * QCAND_SLOTS + 2 * ((size_t)B / 2 + 1)))) return rc;
-        uint64_t* d_qcand = ws->d_qcand;
-        uint32_t* d_qcand_n = reinterpret_cast<uint32_t*>(ws->d_qcand + (size_t)B * QCAND_SLOTS);
-        uint32_t* d_heavy = reinterpret_cast<uint32_t*>(ws->d_qcand + (size_t)B * QCAND_SLOTS + (size_t)B / 2 + 1);
-        const size_t cand_guess0 = std::max<size_t>(1u << 16, (size_t)B * 64);
-        if (ws->cap_cands < cand_guess0 && (rc = grow_pair(ws->d_cands, &ws->cap_cands, cand_guess0))) return rc;
-        uint32_t* d_bin_n = d_qcount + B + 64;
-        const uint32_t sbf = 32u - qb;
-        if (binned) {
-            ScoreBinArgs sa{};
-            sa.bins = h_bin.bins; sa.bin_cap = h_bin.rec32 ? h_bin.bin_cap / 2u : h_bin.bin_cap; sa.rec_mode = h_bin.rec32; sa.bin_count = h_bin.bin_count; sa.bq = h_bin.shift; sa.B = B;
-            sa.nsrc = 1u; sa.src_stride = 0; sa.count_stride = 0; sa.count_step = BIN_STRIDE;
-            sa.opts = d_opts; sa.sb = 32u - qb; sa.cands = ws->d_cands[0]; sa.cand_cap = ws->cap_cands; sa.counters = ws->d_counters;
-            sa.qcand = d_qcand; sa.qcand_n = d_qcand_n; sa.bin_n = d_bin_n; sa.cancel = cancel;
-            // bins of hundreds of thousands of records (hot-hash data: 12 x the records of a uniform batch) get a filter of 2^15 32-bit cells
-            // -- 128 KB, one workgroup per CU -- that counts them in ONE class: two passes over the bin where the 32-KB filter needs 2 K
-            sa.refs = ref_cap ? ws->d_refs : nullptr; sa.ref_cap = ref_cap;
-            sa.flog2 = est_H / sbins > 60000ull ? 16u : 0u;
-            const size_t sb_lds = ((size_t)8u << SB_TABLE_LOG2) + ((size_t)2u << (sa.flog2 ? sa.flog2 : SB_FILTER_LOG2)) + ((size_t)SB_CAND << h_bin.shift) * 8u;
-            {   // (a function's attribute belongs to the device it is set on: once per device, not once per process)
-                static std::atomic<uint64_t> attr_done{0};
-                const uint64_t bit = 1ull << ((unsigned)snap->ctx->device & 63u);
-                if (!(attr_done.load(std::memory_order_acquire) & bit)) {
-                    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&k_score_bin<false>), hipFuncAttributeMaxDynamicSharedMemorySize, 152 * 1024);
-                    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&k_score_bin<true>), hipFuncAttributeMaxDynamicSharedMemorySize, 152 * 1024);
-                    (void)hipGetLastError();
-                    attr_done.fetch_or(bit, std::memory_order_release);
-                }
-            }
-            if (ref_cap) hipLaunchKernelGGL(k_score_bin<true>, dim3(sbins), dim3(SB_WG), sb_lds, st, sa);
-            else hipLaunchKernelGGL(k_score_bin<false>, dim3(sbins), dim3(SB_WG), sb_lds, st, sa);
-        } else {
-        hipLaunchKernelGGL(k_l2_count, dim3(tiles, h_bin.nbins), dim3(256), 0, st, h_bin, d_qcount, B);
-        hipLaunchKernelGGL(k_l2_scan, dim3(1), dim3(1024), 0, st, (const uint32_t*)d_qcount, B, ws->d_qrange, ws->d_qcursor, d_qcand_n,
-                           &ws->d_counters[CTR_TOTAL]);
-        hipLaunchKernelGGL(k_l2_scatter, dim3(tiles, h_bin.nbins), dim3(256), 0, st, h_bin, ws->d_qcursor, B, ws->d_hits[1], (uint64_t)ws->cap_hits);
-        FPX_HIP(hipGetLastError());
-        // k_score as on the general path, its LDS split sized from the estimated records per query
-        uint32_t floor_min = 0xFFFFFFFFu;
-        for (uint32_t q = 0; q < B; ++q) {
-            const uint64_t raw_len = offsets[q + 1] - offsets[q];
-            floor_min = std::min(floor_min, opts[q].has_min_score ? opts[q].min_score : (uint32_t)((raw_len + 19) / 20));
-        }
-        uint32_t log2f = 11;
-        while (log2f < 14 && (1ull << log2f) < 2 * (est_H / B + 1)) ++log2f;
-        log2f = std::max(11u, log2f - (floor_min >= 8u ? 2u : floor_min >= 3u ? 1u : 0u));
-        uint32_t log2t = SCORE_TABLE_LOG2;
-        if (floor_min <= 2u && est_H / B > (1u << SCORE_TABLE_LOG2)) { log2t = 13; log2f = 11; }
-        const size_t cand_guess = std::max<size_t>(1u << 16, (size_t)B * 64);
-        if (ws->cap_cands < cand_guess && (rc = grow_pair(ws->d_cands, &ws->cap_cands, cand_guess))) return rc;
-        static const hipError_t lds_attrs_f[3] = {
-            hipFuncSetAttribute(reinterpret_cast<const void*>(&k_score<32, false>), hipFuncAttributeMaxDynamicSharedMemorySize, 128 * 1024),
-            hipFuncSetAttribute(reinterpret_cast<const void*>(&k_score<8, false>), hipFuncAttributeMaxDynamicSharedMemorySize, 128 * 1024),
-            hipFuncSetAttribute(reinterpret_cast<const void*>(&k_score<32, true>), hipFuncAttributeMaxDynamicSharedMemorySize, 128 * 1024)};
-        (void)lds_attrs_f;
-        const bool short_queries = est_H / B <= (uint64_t)WG * 8u;
-        const size_t score_lds = ((size_t)8 << log2t) + ((size_t)4 << log2f);
-        if (short_queries)
-            hipLaunchKernelGGL((k_score<8, false>), dim3(B), dim3(WG), score_lds, st,
-                               (const uint64_t*)ws->d_hits[1], (const uint64_t*)ws->d_qrange, d_opts, log2f | (log2t << 8), sbf, ws->d_cands[0], (uint64_t)ws->cap_cands, ws->d_counters,
-                               (uint64_t)0, d_qcand, d_qcand_n, d_heavy, cancel);
-        else
-            hipLaunchKernelGGL((k_score<32, false>), dim3(B), dim3(WG), score_lds, st,
-                               (const uint64_t*)ws->d_hits[1], (const uint64_t*)ws->d_qrange, d_opts, log2f | (log2t << 8), sbf, ws->d_cands[0], (uint64_t)ws->cap_cands, ws->d_counters,
-                               (uint64_t)0, d_qcand, d_qcand_n, d_heavy, cancel);
-        // the queries it handed over (far more records than the filter was sized for): their number is on the device
-        hipLaunchKernelGGL((k_score<32, true>), dim3(std::min<uint32_t>(B, 256u)), dim3(WG), score_lds, st,
-                           (const uint64_t*)ws->d_hits[1], (const uint64_t*)ws->d_qrange, d_opts, log2f | (log2t << 8), sbf, ws->d_cands[0], (uint64_t)ws->cap_cands, ws->d_counters,
-                           (uint64_t)0, d_qcand, d_qcand_n, d_heavy, cancel);
-        }       // (!binned)
-        fpx_result* d_res = partial ? out : ws->d_out;
-        uint32_t* d_res_n = partial ? out_n : ws->d_out_n;
-        // (the results travel through pinned staging: a copy to the caller's pageable memory would block the host until the
-        // stream reaches it, and a blocked host cannot watch the deadline.  Small batches: k_finish writes into the staging itself)
-        bool staged = false;
-        if (!partial && (rc = staged_targets(ws, snap->ctx, B, out_cap, &staged, &d_res_n, &d_res))) return rc;
-        // optimistic finish: every query's candidates fit its own slots (C == 0); redone below after a sort otherwise
-        hipLaunchKernelGGL(k_finish, dim3((B + 127) / 128), dim3(128), 0, st,
-                           (const uint64_t*)ws->d_cands[0], (uint64_t)0, d_opts, B, sbf, partial ? 1 : 0, d_res, out_cap, d_res_n,
-                           (const uint64_t*)d_qcand, (const uint32_t*)d_qcand_n, stats ? ws->d_counters : nullptr);
-        FPX_HIP(hipGetLastError());
-        {
-            PublishArgs pa{};
-            pa.counters = ws->d_counters; pa.h_counters = mapped_address(ws->h_counters);
-            pa.a_src = ws->d_def_count; pa.a_dst = spread ? mapped_address(ws->h_def_count) : nullptr; pa.a_n = spread ? (uint32_t)def_words : 0u;      // (not spread: the histogram slots ride in the counters)
-            uint32_t* d_hbins = mapped_address(ws->h_bins);
-            pa.b_src = binned ? d_bin_n : d_bin_count; pa.b_dst = d_hbins + BINQ_HEAD;
-            pa.b_n = binned ? sbins : h_bin.nbins; pa.b_stride = binned ? 1u : BIN_STRIDE;
-            if (!pa.h_counters || (spread && !pa.a_dst) || !d_hbins) { set_error("page-locked host memory is not mapped into the device"); return FPX_E_DEVICE; }
-            hipLaunchKernelGGL(k_publish, dim3(4), dim3(256), 0, st, pa);
-            FPX_HIP(hipGetLastError());
-        }
-        FPX_HIP(hipEventRecord(ws->ev_end, st));
-        FPX_SYNC(ws);
-        // ---- the one look at what happened
-        bool redo = false, hits_short = false;
-        uint64_t worst_bin = 0, bin_total = 0;
-        for (uint32_t i = 0; i < h_bin.nbins; ++i) {
-            const uint64_t c = ws->h_bins[BINQ_HEAD + i];
-            worst_bin = std::max<uint64_t>(worst_bin, c);
-            bin_total += c;
-        }
-        const uint64_t misc = ws->h_counters[CTR_HITS];
-        const uint64_t ref_docs = (binned && ref_cap) ? ws->h_counters[CTR_TOTAL] : 0;         // (docs of the lists that travelled by reference: records of the batch, in no buffer)
-        H = binned ? bin_total + ref_docs : ws->h_counters[CTR_TOTAL];
-        if (worst_bin > h_bin.bin_cap || misc > ws->cap_hits || H - ref_docs > ws->cap_hits) { redo = true; hits_short = true; }
-        if (used_lean)
-            for (uint32_t i = 0; i < snap->n_lean; ++i) redo = redo || ws->h_def_count[(size_t)i * DEF_COUNT_STRIDE] > def_cap;
-        if (ws->h_counters[CTR_MAXSCORE] != 0 || ws->h_counters[CTR_CANDS] > ws->cap_cands || ws->h_counters[CTR_BINFAIL] != 0) redo = true;
-        if (ws->h_counters[CTR_BINFAIL] == 3) __atomic_store_n(const_cast<uint32_t*>(&snap->rec32_refused), 1u, __ATOMIC_RELAXED);      // (a doc id beyond the declared range)
-        if (redo) {
-            if (hits_short) {           // room for what this batch really produced, so that neither path trips over it again
-                const size_t need = (size_t)std::max<uint64_t>(std::max<uint64_t>(worst_bin * h_bin.nbins, misc), H) * 5 / 4 + 1024;
-                if (ws->cap_hits < need && (rc = grow_pair(ws->d_hits, &ws->cap_hits, need))) return rc;
-            }
-            ws->hint_H = 0;             // the estimate was off: the general path measures again
-            ws->fast_penalty = 4;
-            return FPX_REDO;
-        }
-        uint64_t Cf = 0;
-        int ccur2 = 0;
-        if (ws->h_counters[CTR_CANDS] != 0) {
-            // some queries have more candidates than slots: sort the shared list and finish again (second round trip)
-            Cf = ws->h_counters[CTR_CANDS];
-            const size_t tb2 = sort_u64_temp_bytes(Cf, 0, 64);
-            if ((rc = grow(reinterpret_cast<uint8_t**>(&ws->d_temp), &ws->cap_temp, tb2 + 256))) return rc;
-            FPX_HIP(sort_u64(ws->d_temp, ws->cap_temp, ws->d_cands[0], ws->d_cands[1], Cf, 0, 64, st, &ccur2));
-            if (stats) FPX_HIP(hipMemsetAsync(&ws->d_counters[CTR_SLOTCANDS], 0, sizeof(unsigned long long), st));
-            hipLaunchKernelGGL(k_finish, dim3((B + 127) / 128), dim3(128), 0, st,
-                               (const uint64_t*)ws->d_cands[ccur2], Cf, d_opts, B, sbf, partial ? 1 : 0, d_res, out_cap, d_res_n,
-                               (const uint64_t*)d_qcand, (const uint32_t*)d_qcand_n, stats ? ws->d_counters : nullptr);
-            FPX_HIP(hipGetLastError());
-            FPX_HIP(hipMemcpyAsync(&ws->h_counters[CTR_SLOTCANDS], &ws->d_counters[CTR_SLOTCANDS], sizeof(unsigned long long), hipMemcpyDeviceToHost, st));
-            FPX_HIP(hipEventRecord(ws->ev_end, st));
-            FPX_SYNC(ws);
-        }
-        if (!partial && (rc = deliver_results(ws, B, out_cap, staged, out, out_n, st))) return rc;
-        {
-            const unsigned long long* ls = spread ? reinterpret_cast<const unsigned long long*>(ws->h_def_count + def_stat_off) : nullptr;
-            unsigned long long probes = ws->h_counters[CTR_PROBES];
-            if (ls) for (uint32_t i = 0; i < LEAN_STAT_SETS; ++i) probes += ls[i * 8 + 3];
-            gather_hist(ws->batch_hist, ws->h_counters, ls, probes);
-        }
-        if (stats) {
-            unsigned long long reads = 0, blocks = 0, docs = 0, probes = 0, bytes_off = 0;
-            unsigned long long pads = ws->h_counters[CTR_PADS];          // ("no record" entries in the bins' counts: fpx_partition.hpp, BIN_ALIGN)
-            if (spread) {
-                const unsigned long long* ls = reinterpret_cast<const unsigned long long*>(ws->h_def_count + def_stat_off);
-                unsigned long long dreads = 0;
-                for (uint32_t i = 0; i < LEAN_STAT_SETS; ++i) {
-                    reads += ls[i * 8 + 0]; blocks += ls[i * 8 + 1]; docs += ls[i * 8 + 2]; probes += ls[i * 8 + 3]; dreads += ls[i * 8 + 4];
-                    bytes_off += ls[i * 8 + 5];      // (direct-addressed segments of a block size other than 512: the difference, mod 2^64)
-                    pads += ls[i * 8 + 6];
-                }
-                reads += (dreads + 1) / 2;
-            }
-            float ms = 0.f, aux = 0.f, total_ms = 0.f;
-            if (P && (snap->n_file || snap->n_direct)) {
-                (void)hipEventElapsedTime(&ms, ws->ev_probe0, ws->ev_probe1);
-                if (used_lean) (void)hipEventElapsedTime(&aux, ws->ev_probe1, ws->ev_probe2);
-            }
-            (void)hipEventElapsedTime(&total_ms, ws->ev_begin, ws->ev_end);
-            const bool ln = spread;
-            stats->probes += ws->h_counters[CTR_PROBES] + probes;
-            stats->scanned_blocks += ws->h_counters[CTR_BLOCKS] + blocks;
-            stats->scanned_docs += ws->h_counters[CTR_DOCS] + docs;
-            stats->hits += H - (binned ? std::min<unsigned long long>(pads, H) : 0ull);
-            stats->algorithmic_bytes += ws->h_counters[CTR_BYTES] + blocks * 512ull + bytes_off;
-            stats->candidates += Cf + ws->h_counters[CTR_SLOTCANDS];
-            stats->probe_kernel_ms += ms;
-            stats->total_gpu_ms += total_ms;
-            stats->probe_launches += probe_launches;
-            stats->generic_iters += (uint32_t)ws->h_counters[CTR_GENERIC];
-            stats->probe_kernel_bytes += ln ? blocks * 512ull + bytes_off : ws->h_counters[CTR_BYTES];
-            stats->probe_kernel_fetched_bytes += ln ? reads * 128ull : snap->n_direct ? ws->h_counters[CTR_LEAN_READS] * 64ull + (snap->n_file ? ws->h_counters[CTR_BYTES] : 0ull)
-                                                                     : ws->h_counters[CTR_BYTES];
-            stats->probe_aux_ms += aux;
-            stats->path_flags |= 1u | (Cf ? 2u : 0u) | (used_fused ? 4u : 0u) | (binned ? 8u : 0u) | (ref_docs ? 32u : 0u);
-        }
-        if ((rc = deliver_qstats())) return rc;
-        ws->hint_P = P; ws->hint_H = std::max<uint64_t>(H, 1);
-        ws->hint_misc = binned ? misc : 0;
-        ws->hint_def = 0;
-        if (used_lean) for (uint32_t i = 0; i < snap->n_lean; ++i) ws->hint_def = std::max<uint32_t>(ws->hint_def, ws->h_def_count[(size_t)i * DEF_COUNT_STRIDE]);
-        return FPX_OK;
-    }
-    if (single_fast) {
-        if (ws->cap_cands < SINGLE_CANDS && (rc = grow_pair(ws->d_cands, &ws->cap_cands, SINGLE_CANDS))) return rc;
-        static const hipError_t lds_attr1 = hipFuncSetAttribute(reinterpret_cast<const void*>(&k_score<32, true>),
-                                                                hipFuncAttributeMaxDynamicSharedMemorySize, 128 * 1024);
-        (void)lds_attr1;
-        const uint32_t log2f = 13, sb1 = 32u - qb;
-        hipLaunchKernelGGL((k_score<32, true>), dim3(1), dim3(WG), ((size_t)8 << SCORE_TABLE_LOG2) + ((size_t)4 << log2f), st,
-                           (const uint64_t*)ws->d_hits[0], (const uint64_t*)nullptr, d_opts, log2f | (SCORE_TABLE_LOG2 << 8), sb1, ws->d_cands[0],
-                           (uint64_t)SINGLE_CANDS, ws->d_counters, (uint64_t)ws->cap_hits, (uint64_t*)nullptr, (uint32_t*)nullptr, (uint32_t*)nullptr, cancel);
-        if (!ws->d_ret) FPX_HIP(hipHostGetDevicePointer(reinterpret_cast<void**>(&ws->d_ret), ws->h_counters, 0));
-        hipLaunchKernelGGL(k_finish_single, dim3(1), dim3(256), 0, st, (const uint64_t*)ws->d_cands[0], d_opts,
-                           (const unsigned long long*)ws->d_counters, out_cap, ws->d_ret);
-        FPX_HIP(hipGetLastError());
-        FPX_SYNC(ws);      // counters, result count and results are in pinned host memory now
-        if (timeout_ms && now_ms() - t_start > (double)timeout_ms) return FPX_E_TIMEOUT;
-        H = ws->h_counters[CTR_HITS];
-        const bool fits = H <= ws->cap_hits && ws->h_counters[CTR_CANDS] <= SINGLE_CANDS && ws->h_counters[CTR_MAXSCORE] == 0;
-        if (!fits) {                           // rare: rerun on the general path (which grows buffers / splits as needed)
-            if (H > ws->cap_hits && (rc = grow_pair(ws->d_hits, &ws->cap_hits, (size_t)H + 1024))) return rc;
-            return run_batch(snap, ws, resident, q0, hashes, offsets, B, opts, timeout_ms, partial, out, out_cap, out_n, stats, ex, true, t_start, q_blocks, q_docs);
-        }
-        *out_n = (uint32_t)ws->h_counters[CTR_COUNT];
-        std::memcpy(out, ws->h_counters + CTR_COUNT + 1, (size_t)*out_n * sizeof(fpx_result));
-        gather_hist(ws->batch_hist, ws->h_counters, nullptr, ws->h_counters[CTR_PROBES]);
-        if (stats) {                             // counters only: the fast path takes no device timestamps
-            const float total_ms = 0.f, ms = 0.f;
-            stats->probes += ws->h_counters[CTR_PROBES];
-            stats->scanned_blocks += ws->h_counters[CTR_BLOCKS];
-            stats->scanned_docs += ws->h_counters[CTR_DOCS];
-            stats->hits += H;
-            stats->algorithmic_bytes += ws->h_counters[CTR_BYTES];
-            stats->candidates += ws->h_counters[CTR_CANDS];
-            stats->probe_kernel_ms += ms;
-            stats->total_gpu_ms += total_ms;
-            stats->probe_launches += probe_launches;
-            stats->generic_iters += (uint32_t)ws->h_counters[CTR_GENERIC];
-            stats->probe_kernel_bytes += ws->h_counters[CTR_BYTES];
-            stats->probe_kernel_fetched_bytes += snap->n_direct ? ws->h_counters[CTR_LEAN_READS] * 64ull + (snap->n_file ? ws->h_counters[CTR_BYTES] : 0ull)
-                                                                : ws->h_counters[CTR_BYTES];
-        }
-        return FPX_OK;
-    }
-    if (score_only) {                           // the records come from the exchange instead of the probes above
-        H = ex->n;
-        if (H > ws->cap_hits && (rc = grow_pair(ws->d_hits, &ws->cap_hits, (size_t)H + 1024))) return rc;
-        if (H) FPX_HIP(hipMemcpyAsync(ws->d_hits[0], ex->d_records, H * sizeof(uint64_t), hipMemcpyDeviceToDevice, st));
-    }
-    if (timeout_ms && now_ms() - t_start > (double)timeout_ms) return FPX_E_TIMEOUT;
-    // statistics: slots 0..7 are written by k_probe (generic / deferred / memory), 8..15 by k_probe_lean8
-    const unsigned long long c_blocks = ws->h_counters[CTR_BLOCKS] + ws->h_counters[8 + CTR_BLOCKS],
-                             c_docs = ws->h_counters[CTR_DOCS] + ws->h_counters[8 + CTR_DOCS],
-                             c_bytes = ws->h_counters[CTR_BYTES] + ws->h_counters[8 + CTR_BYTES],
-                             c_probes = ws->h_counters[CTR_PROBES] + ws->h_counters[8 + CTR_PROBES],
-                             c_generic = ws->h_counters[CTR_GENERIC],
-                             c_main_bytes = spread ? ws->h_counters[8 + CTR_BYTES] : ws->h_counters[CTR_BYTES],
-                             c_fetched_bytes = spread ? ws->h_counters[CTR_LEAN_READS] * 128ull            // (lines)
-                                               : snap->n_direct ? ws->h_counters[CTR_LEAN_READS] * 64ull + (snap->n_file ? ws->h_counters[CTR_BYTES] : 0ull)   // (k_probe_direct / _fused without the spread statistics: 64-byte units)
-                                               : ws->h_counters[CTR_BYTES];
-
-    if (!score_only)
-        gather_hist(ws->batch_hist, ws->h_counters, spread ? reinterpret_cast<const unsigned long long*>(ws->h_def_count + def_stat_off) : nullptr, c_probes);
-    uint64_t C = 0, C_slots = 0;                   // candidates in the shared list / in the queries' own slots
-    uint64_t* d_qcand = nullptr;
-    uint32_t* d_qcand_n = nullptr;
-    auto fill_stats = [&]() {
-        if (!stats) return;
-        float total_ms = 0.f;
-        (void)hipEventElapsedTime(&total_ms, ws->ev_begin, ws->ev_end);
-        stats->probes += c_probes;
-        stats->scanned_blocks += c_blocks;
-        stats->scanned_docs += c_docs;
-        stats->hits += H;
-        stats->algorithmic_bytes += c_bytes;
-        stats->candidates += C + C_slots;
-        stats->probe_kernel_ms += probe_ms;
-        stats->total_gpu_ms += total_ms;
-        stats->probe_launches += probe_launches;
-        stats->generic_iters += (uint32_t)c_generic;
-        stats->probe_kernel_bytes += c_main_bytes;
-        stats->probe_kernel_fetched_bytes += c_fetched_bytes;
-        stats->probe_aux_ms += aux_ms;
-        if (used_fused) stats->path_flags |= 4u;
-    };
-
-    if (probe_only) {
-        // group the records by destination rank (doc & (world - 1)) and hand them to the caller
-        const uint32_t world = ex->world, mask = world - 1u;
-        if (world > 1 && H) {
-            int hcur = 0;
-            const unsigned wb = bits_for(world);
-            const size_t tb = sort_u64_temp_bytes(H, 0, wb);
-            if ((rc = grow(reinterpret_cast<uint8_t**>(&ws->d_temp), &ws->cap_temp, tb + 256))) return rc;
-            FPX_HIP(sort_u64(ws->d_temp, ws->cap_temp, ws->d_hits[0], ws->d_hits[1], H, 0, wb, st, &hcur));
-            if (hcur != 0) std::swap(ws->d_hits[0], ws->d_hits[1]);
-        }
-        if ((rc = grow(&ws->d_qrange, &ws->cap_qrange, (size_t)world + 2))) return rc;
-        hipLaunchKernelGGL(k_dest_bounds, dim3((world + 1 + 63) / 64), dim3(64), 0, st,
-                           (const uint64_t*)ws->d_hits[0], H, mask, world, ws->d_qrange);
-        FPX_HIP(hipGetLastError());
-        std::vector<uint64_t> hb(world + 1);
-        FPX_HIP(hipMemcpyAsync(hb.data(), ws->d_qrange, ((size_t)world + 1) * sizeof(uint64_t), hipMemcpyDeviceToHost, st));
-        const bool fits = H <= ex->cap;
-        if (fits && H) FPX_HIP(hipMemcpyAsync(ex->d_records, ws->d_hits[0], H * sizeof(uint64_t), hipMemcpyDeviceToDevice, st));
-        FPX_HIP(hipEventRecord(ws->ev_end, st));
-        FPX_SYNC(ws);
-        for (uint32_t d = 0; d < world; ++d) ex->counts[d] = hb[d + 1] - hb[d];
-        if (!fits) { set_error("records buffer too small: %llu records (counts are filled in; retry with room for them)", (unsigned long long)H); return FPX_E_INVAL; }
-        fill_stats();
-        return FPX_OK;
-    }
-
-    // ---- 5: partition the hit records by query, count per (query, doc) in LDS, keep score >= min_score
-    int ccur = 0;
-    sb = 32u - qb;                              // score field of the candidate key; larger scores -> split the batch
-    if (H) {
-        // partition of the records by query (order inside a query is irrelevant to the hash-table count)
-        if ((rc = grow(&ws->d_qrange, &ws->cap_qrange, (size_t)B * 2 + 2))) return rc;
-        if (qb) {
-            int hcur = 0;
-            const size_t tb = sort_u64_temp_bytes(H, 32, 32 + qb);
-            if ((rc = grow(reinterpret_cast<uint8_t**>(&ws->d_temp), &ws->cap_temp, tb + 256))) return rc;
-            FPX_HIP(sort_u64(ws->d_temp, ws->cap_temp, ws->d_hits[0], ws->d_hits[1], H, 32, 32 + qb, st, &hcur));
-            if (hcur != 0) std::swap(ws->d_hits[0], ws->d_hits[1]);   // convention: d_hits[0] holds the data
-        }
-        // per-query candidate slots: [B][QCAND_SLOTS] keys, then [B] counts; then the list of heavy queries [B]
-        if ((rc = grow(&ws->d_qcand, &ws->cap_qcand, (size_t)B * QCAND_SLOTS + 2 * ((size_t)B / 2 + 1)))) return rc;
-        d_qcand = ws->d_qcand;
-        d_qcand_n = reinterpret_cast<uint32_t*>(ws->d_qcand + (size_t)B * QCAND_SLOTS);
-        hipLaunchKernelGGL(k_bounds, dim3((B + WG - 1) / WG), dim3(WG), 0, st, (const uint64_t*)ws->d_hits[0], H, B, ws->d_qrange, d_qcand_n);
-        // counting filter sized for ~2x the average number of records per query (8 KB .. 64 KB of LDS) + 16 KB exact table
-        // The filter only has to keep cells that collect < min_score records below the floor: with the usual floor
-        // (n / 20 = 50 for 1 k-hash queries) a cell may hold several docs' records and still reject them, so a quarter of
-        // the size does; the LDS saved more than doubles the resident workgroups (k_score is occupancy bound).
-        uint32_t floor_min = 0xFFFFFFFFu;
-        for (uint32_t q = 0; q < B; ++q) {
-            const uint64_t raw_len = offsets[q + 1] - offsets[q];
-            floor_min = std::min(floor_min, opts[q].has_min_score ? opts[q].min_score : (uint32_t)((raw_len + 19) / 20));
-        }
-        uint32_t log2f = 11;
-        while (log2f < 14 && (1ull << log2f) < 2 * (H / B + 1)) ++log2f;
-        log2f = std::max(11u, log2f - (floor_min >= 8u ? 2u : floor_min >= 3u ? 1u : 0u));
-        // ... and with a floor of 1 or 2 (the legacy protocol) nearly every record passes it: the LDS goes to a larger
-        // exact table instead, so that the count needs 2 passes rather than 6.
-        uint32_t log2t = SCORE_TABLE_LOG2;
-        if (floor_min <= 2u && H / B > (1u << SCORE_TABLE_LOG2)) { log2t = 13; log2f = 11; }
-        const size_t cand_guess = std::max<size_t>(1u << 16, (size_t)B * 64);
-        if (ws->cap_cands < cand_guess && (rc = grow_pair(ws->d_cands, &ws->cap_cands, cand_guess))) return rc;
-        static const hipError_t lds_attrs[3] = {
-            hipFuncSetAttribute(reinterpret_cast<const void*>(&k_score<32, false>), hipFuncAttributeMaxDynamicSharedMemorySize, 128 * 1024),
-            hipFuncSetAttribute(reinterpret_cast<const void*>(&k_score<8, false>), hipFuncAttributeMaxDynamicSharedMemorySize, 128 * 1024),
-            hipFuncSetAttribute(reinterpret_cast<const void*>(&k_score<32, true>), hipFuncAttributeMaxDynamicSharedMemorySize, 128 * 1024)};
-        (void)lds_attrs;
-        const bool short_queries = H / B <= (uint64_t)WG * 8u;      // the average query fits one 8-row tile
-        uint32_t* d_heavy = reinterpret_cast<uint32_t*>(ws->d_qcand + (size_t)B * QCAND_SLOTS + (size_t)B / 2 + 1);
-        const size_t score_lds = ((size_t)8 << log2t) + ((size_t)4 << log2f);
-        for (int attempt = 0;; ++attempt) {
-            if (attempt > 0) {                    // first attempt: the counters are still zero, k_bounds zeroed the slot counts
-                FPX_HIP(hipMemsetAsync(&ws->d_counters[CTR_CANDS], 0, sizeof(unsigned long long), st));
-                FPX_HIP(hipMemsetAsync(&ws->d_counters[CTR_MAXSCORE], 0, sizeof(unsigned long long), st));
-                FPX_HIP(hipMemsetAsync(&ws->d_counters[CTR_HEAVY], 0, sizeof(unsigned long long), st));
-                FPX_HIP(hipMemsetAsync(d_qcand_n, 0, (size_t)B * sizeof(uint32_t), st));
-            }
-            if (short_queries)
-                hipLaunchKernelGGL((k_score<8, false>), dim3(B), dim3(WG), score_lds, st,
-                                   (const uint64_t*)ws->d_hits[0], (const uint64_t*)ws->d_qrange, d_opts, log2f | (log2t << 8), sb, ws->d_cands[0], (uint64_t)ws->cap_cands, ws->d_counters,
-                                   (uint64_t)0, d_qcand, d_qcand_n, d_heavy, cancel);
-            else
-                hipLaunchKernelGGL((k_score<32, false>), dim3(B), dim3(WG), score_lds, st,
-                                   (const uint64_t*)ws->d_hits[0], (const uint64_t*)ws->d_qrange, d_opts, log2f | (log2t << 8), sb, ws->d_cands[0], (uint64_t)ws->cap_cands, ws->d_counters,
-                                   (uint64_t)0, d_qcand, d_qcand_n, d_heavy, cancel);
-            FPX_HIP(hipGetLastError());
-            FPX_HIP(hipMemcpyAsync(ws->h_counters, ws->d_counters, CTR_COUNT * sizeof(unsigned long long), hipMemcpyDeviceToHost, st));
-            FPX_SYNC(ws);
-            if (ws->h_counters[CTR_HEAVY] != 0) {
-                // queries the launch above handed over (far more records than the filter was sized for): rounds over doc classes
-                hipLaunchKernelGGL((k_score<32, true>), dim3((uint32_t)std::min<uint64_t>(ws->h_counters[CTR_HEAVY], 1024u)), dim3(WG), score_lds, st,
-                                   (const uint64_t*)ws->d_hits[0], (const uint64_t*)ws->d_qrange, d_opts, log2f | (log2t << 8), sb, ws->d_cands[0], (uint64_t)ws->cap_cands, ws->d_counters,
-                                   (uint64_t)0, d_qcand, d_qcand_n, d_heavy, cancel);
-                FPX_HIP(hipGetLastError());
-                FPX_HIP(hipMemcpyAsync(ws->h_counters, ws->d_counters, CTR_COUNT * sizeof(unsigned long long), hipMemcpyDeviceToHost, st));
-                FPX_SYNC(ws);
-            }
-            C = ws->h_counters[CTR_CANDS];
-            if (ws->h_counters[CTR_MAXSCORE] != 0) {              // a score does not fit the key's score field
-                if (B <= 1) { set_error("score overflows u32"); return FPX_E_INVAL; }
-                if (score_only) { set_error("a score does not fit the candidate key: use smaller query batches"); return FPX_E_INVAL; }
-                return FPX_SPLIT;                                  // the caller retries with smaller batches
-            }
-            if (C <= ws->cap_cands) break;
-            if (attempt >= 2) { set_error("candidate buffer overflow persists"); return FPX_E_DEVICE; }
-            if ((rc = grow_pair(ws->d_cands, &ws->cap_cands, (size_t)C + 1024))) return rc;
-        }
-        // ---- 6: sort candidates by (q, score desc, id asc)
-        if (C) {
-            const size_t tb2 = sort_u64_temp_bytes(C, 0, 64);
-            if ((rc = grow(reinterpret_cast<uint8_t**>(&ws->d_temp), &ws->cap_temp, tb2 + 256))) return rc;
-            FPX_HIP(sort_u64(ws->d_temp, ws->cap_temp, ws->d_cands[0], ws->d_cands[1], C, 0, 64, st, &ccur));
+    return FPX_OK;
+}
+// a bin per workgroup: k_score_bin over the bins k_probe_group filled
+static void score_bins(Batch& b, const Bins& bins, const CandSlots& cs, uint32_t* d_bin_n)
+{
+    Snapshot* snap = b.snap; Workspace* ws = b.ws;
+    const BinArgs& h_bin = bins.h;
+    ScoreBinArgs sa{};
+    sa.bins = h_bin.bins; sa.bin_cap = h_bin.rec32 ? h_bin.bin_cap / 2u : h_bin.bin_cap; sa.rec_mode = h_bin.rec32; sa.bin_count = h_bin.bin_count; sa.bq = h_bin.shift; sa.B = b.B;
+    sa.nsrc = 1u; sa.src_stride = 0; sa.count_stride = 0; sa.count_step = BIN_STRIDE;
+    sa.opts = b.d_opts; sa.sb = 32u - b.qb; sa.cands = ws->d_cands[0]; sa.cand_cap = ws->cap_cands; sa.counters = ws->d_counters;
+    sa.qcand = cs.qcand; sa.qcand_n = cs.qcand_n; sa.bin_n = d_bin_n; sa.cancel = b.cancel;
+    // bins of hundreds of thousands of records (hot-hash data: 12 x the records of a uniform batch) get a filter of 2^15 32-bit cells
+    // -- 128 KB, one workgroup per CU -- that counts them in ONE class: two passes over the bin where the 32-KB filter needs 2 K
+    sa.refs = bins.ref_cap ? ws->d_refs : nullptr; sa.ref_cap = bins.ref_cap;
+    sa.flog2 = bins.est_H / bins.sbins > 60000ull ? 16u : 0u;
+    const size_t sb_lds = ((size_t)8u << SB_TABLE_LOG2) + ((size_t)2u << (sa.flog2 ? sa.flog2 : SB_FILTER_LOG2)) + ((size_t)SB_CAND << h_bin.shift) * 8u;
+    {   // (a function's attribute belongs to the device it is set on: once per device, not once per process)
+        static std::atomic<uint64_t> attr_done{0};
+        const uint64_t bit = 1ull << ((unsigned)snap->ctx->device & 63u);
+        if (!(attr_done.load(std::memory_order_acquire) & bit)) {
+            (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&k_score_bin<false>), hipFuncAttributeMaxDynamicSharedMemorySize, 152 * 1024);
+            (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&k_score_bin<true>), hipFuncAttributeMaxDynamicSharedMemorySize, 152 * 1024);
+            (void)hipGetLastError();
+            attr_done.fetch_or(bit, std::memory_order_release);
         }
     }
-    if (timeout_ms && now_ms() - t_start > (double)timeout_ms) return FPX_E_TIMEOUT;
-
-    // ---- finish
-    fpx_result* d_res = partial ? out : ws->d_out;
-    uint32_t* d_res_n = partial ? out_n : ws->d_out_n;
-    hipLaunchKernelGGL(k_finish, dim3((B + 127) / 128), dim3(128), 0, st,
-                       (const uint64_t*)ws->d_cands[ccur], C, d_opts, B, sb, partial ? 1 : 0, d_res, out_cap, d_res_n,
-                       (const uint64_t*)d_qcand, (const uint32_t*)d_qcand_n, (stats && d_qcand_n) ? ws->d_counters : nullptr);
+    if (bins.ref_cap) hipLaunchKernelGGL(k_score_bin<true>, dim3(bins.sbins), dim3(SB_WG), sb_lds, b.st, sa);
+    else hipLaunchKernelGGL(k_score_bin<false>, dim3(bins.sbins), dim3(SB_WG), sb_lds, b.st, sa);
+}
+// bins -> per-query ranges (level 2 of fpx_partition.hpp), then k_score as on the general path, its LDS split sized from the estimated
+// records per query
+static int score_two_level(Batch& b, const Bins& bins, const CandSlots& cs, uint32_t sbf)
+{
+    Workspace* ws = b.ws; hipStream_t st = b.st; const uint32_t B = b.B; const BinArgs& h_bin = bins.h;
+    const uint32_t tiles = (uint32_t)std::min<uint64_t>((h_bin.bin_cap + L2_TILE - 1) / L2_TILE, 0x7FFFFFFFull / 256u);
+    hipLaunchKernelGGL(k_l2_count, dim3(tiles, h_bin.nbins), dim3(256), 0, st, h_bin, bins.d_qcount, B);
+    hipLaunchKernelGGL(k_l2_scan, dim3(1), dim3(1024), 0, st, (const uint32_t*)bins.d_qcount, B, ws->d_qrange, ws->d_qcursor, cs.qcand_n,
+                       &ws->d_counters[CTR_TOTAL]);
+    hipLaunchKernelGGL(k_l2_scatter, dim3(tiles, h_bin.nbins), dim3(256), 0, st, h_bin, ws->d_qcursor, B, ws->d_hits[1], (uint64_t)ws->cap_hits);
     FPX_HIP(hipGetLastError());
-    bool staged = false;
-    if (!partial && (rc = stage_results(ws, B, out_cap, st, &staged))) return rc;
-    if (stats && d_qcand_n)
-        FPX_HIP(hipMemcpyAsync(&ws->h_counters[CTR_SLOTCANDS], &ws->d_counters[CTR_SLOTCANDS], sizeof(unsigned long long), hipMemcpyDeviceToHost, st));
-    FPX_HIP(hipEventRecord(ws->ev_end, st));
-    FPX_SYNC(ws);
-    if (timeout_ms && now_ms() - t_start > (double)timeout_ms) return FPX_E_TIMEOUT;
-    if (!partial && (rc = deliver_results(ws, B, out_cap, staged, out, out_n, st))) return rc;
-    if (stats && d_qcand_n) C_slots = ws->h_counters[CTR_SLOTCANDS];
+    uint32_t log2f, log2t;
+    score_filter_sizes(min_floor(b.offsets, b.opts, B), bins.est_H, B, &log2f, &log2t);
+    const bool short_queries = bins.est_H / B <= (uint64_t)WG * 8u;
+    const size_t score_lds = ((size_t)8 << log2t) + ((size_t)4 << log2f);
+    if (short_queries) launch_score<8, false>(b, B, score_lds, ws->d_hits[1], log2f | (log2t << 8), sbf, cs);
+    else launch_score<32, false>(b, B, score_lds, ws->d_hits[1], log2f | (log2t << 8), sbf, cs);
+    // the queries it handed over (far more records than the filter was sized for): their number is on the device
+    launch_score<32, true>(b, std::min<uint32_t>(B, 256u), score_lds, ws->d_hits[1], log2f | (log2t << 8), sbf, cs);
+    return FPX_OK;
+}
 
-    fill_stats();
-    if ((rc = deliver_qstats())) return rc;
-    ws->hint_P = P; ws->hint_H = std::max<uint64_t>(H, 1);       // sizes the device-sized path of the next batch
+static int run_device_sized(Batch& b, const Keys& keys)
+{
+    Snapshot* snap = b.snap; Workspace* ws = b.ws; hipStream_t st = b.st; const uint32_t B = b.B; int rc;
+    Bins bins;
+    if ((rc = size_bins(b, keys, &bins))) return rc;
+    const BinArgs& h_bin = bins.h;
+    const bool binned = bins.binned;
+    Probes pr;
+    pr.bins = &bins;
+    if ((rc = launch_probes(b, keys, pr))) return rc;
+    const bool spread = pr.spread, used_lean = pr.used_lean;
+    // ---- 5': bins -> scores, finish; sizes stay on the device
+    // (binned: only what k_probe_group could not place itself is in the misc buffer -- normally nothing; the lists of hot hashes,
+    // which go there whole, on skewed data: the grid follows what the workspace's last batch left there)
+    const uint32_t bin_grid = binned ? (uint32_t)std::min<uint64_t>(std::max<uint64_t>(64, (2 * ws->hint_misc + BIN_TILE - 1) / BIN_TILE), 8192u)
+                                     : (uint32_t)std::min<uint64_t>((2 * bins.est_H + BIN_TILE - 1) / BIN_TILE, 8192u);
+    hipLaunchKernelGGL(k_bin, dim3(std::max(1u, bin_grid)), dim3(256), 0, st, h_bin, (const uint64_t*)ws->d_hits[1],
+                       (const unsigned long long*)&ws->d_counters[CTR_HITS], (uint64_t)ws->cap_hits);
+    if ((rc = grow(&ws->d_qrange, &ws->cap_qrange, (size_t)B * 2 + 2))) return rc;
+    CandSlots cs;
+    if ((rc = ensure_cand_slots(ws, B, 0, &cs))) return rc;
+    uint32_t* d_bin_n = bins.d_qcount + B + 64;
+    const uint32_t sbf = 32u - b.qb;
+    if (binned) score_bins(b, bins, cs, d_bin_n);
+    else if ((rc = score_two_level(b, bins, cs, sbf))) return rc;
+    // (the results travel through pinned staging: a copy to the caller's pageable memory would block the host until the
+    // stream reaches it, and a blocked host cannot watch the deadline.  Small batches: k_finish writes into the staging itself)
+    ResultsTo to;
+    if ((rc = results_target(b, &to))) return rc;
+    // optimistic finish: every query's candidates fit its own slots (C == 0); redone below after a sort otherwise
+    launch_finish(b, ws->d_cands[0], 0, sbf, cs, to.res, to.n, b.stats != nullptr);
+    FPX_HIP(hipGetLastError());
+    // (not spread: the histogram slots ride in the counters)
+    if ((rc = publish(b, spread, binned ? d_bin_n : bins.d_bin_count, binned ? bins.sbins : h_bin.nbins, binned ? 1u : BIN_STRIDE))) return rc;
+    FPX_HIP(hipEventRecord(ws->ev_end, st));
+    FPX_SYNC_BATCH(b);
+    // ---- the one look at what happened
+    bool redo = false, hits_short = false;
+    uint64_t worst_bin = 0, bin_total = 0;
+    for (uint32_t i = 0; i < h_bin.nbins; ++i) {
+        const uint64_t c = ws->h_bins[BINQ_HEAD + i];
+        worst_bin = std::max<uint64_t>(worst_bin, c);
+        bin_total += c;
+    }
+    const uint64_t misc = ws->h_counters[CTR_HITS];
+    const uint64_t ref_docs = (binned && bins.ref_cap) ? ws->h_counters[CTR_TOTAL] : 0;         // (docs of the lists that travelled by reference: records of the batch, in no buffer)
+    const uint64_t H = binned ? bin_total + ref_docs : ws->h_counters[CTR_TOTAL];
+    if (worst_bin > h_bin.bin_cap || misc > ws->cap_hits || H - ref_docs > ws->cap_hits) { redo = true; hits_short = true; }
+    if (used_lean)
+        for (uint32_t i = 0; i < snap->n_lean; ++i) redo = redo || ws->h_def_count[(size_t)i * DEF_COUNT_STRIDE] > b.def_cap;
+    if (ws->h_counters[CTR_MAXSCORE] != 0 || ws->h_counters[CTR_CANDS] > ws->cap_cands || ws->h_counters[CTR_BINFAIL] != 0) redo = true;
+    if (ws->h_counters[CTR_BINFAIL] == 3) __atomic_store_n(const_cast<uint32_t*>(&snap->rec32_refused), 1u, __ATOMIC_RELAXED);      // (a doc id beyond the declared range)
+    if (redo) {
+        if (hits_short) {           // room for what this batch really produced, so that neither path trips over it again
+            const size_t need = (size_t)std::max<uint64_t>(std::max<uint64_t>(worst_bin * h_bin.nbins, misc), H) * 5 / 4 + 1024;
+            if (ws->cap_hits < need && (rc = grow_pair(ws->d_hits, &ws->cap_hits, need))) return rc;
+        }
+        ws->hint_H = 0;             // the estimate was off: the general path measures again
+        ws->fast_penalty = 4;
+        return FPX_REDO;
+    }
+    const uint64_t Cf = ws->h_counters[CTR_CANDS];
+    if (Cf != 0 && (rc = finish_crowded(b, sbf, cs, to, Cf))) return rc;
+    if (!b.partial && (rc = deliver_results(ws, B, b.out_cap, to.staged, b.out, b.out_n, st))) return rc;
+    const unsigned long long* ls = spread ? host_stat_sets(b) : nullptr;
+    const StatSums s = ls ? sum_stat_sets(ls) : StatSums{};
+    gather_hist(ws->batch_hist, ws->h_counters, ls, ws->h_counters[CTR_PROBES] + s.probes);
+    if (fpx_stats* stats = b.stats) {
+        const unsigned long long reads = s.reads + (spread ? (s.dreads + 1) / 2 : 0ull);
+        const unsigned long long pads = ws->h_counters[CTR_PADS] + s.pads;          // ("no record" entries in the bins' counts: fpx_partition.hpp, BIN_ALIGN)
+        float ms = 0.f, aux = 0.f, total_ms = 0.f;
+        if (b.P && (snap->n_file || snap->n_direct)) {
+            (void)hipEventElapsedTime(&ms, ws->ev_probe0, ws->ev_probe1);
+            if (used_lean) (void)hipEventElapsedTime(&aux, ws->ev_probe1, ws->ev_probe2);
+        }
+        (void)hipEventElapsedTime(&total_ms, ws->ev_begin, ws->ev_end);
+        stats->probes += ws->h_counters[CTR_PROBES] + s.probes; stats->scanned_blocks += ws->h_counters[CTR_BLOCKS] + s.blocks; stats->scanned_docs += ws->h_counters[CTR_DOCS] + s.docs;
+        stats->hits += H - (binned ? std::min<unsigned long long>(pads, H) : 0ull);
+        stats->algorithmic_bytes += ws->h_counters[CTR_BYTES] + s.blocks * 512ull + s.bytes_off;
+        stats->candidates += Cf + ws->h_counters[CTR_SLOTCANDS];
+        stats->probe_kernel_ms += ms; stats->total_gpu_ms += total_ms; stats->probe_aux_ms += aux; stats->probe_launches += pr.launches;
+        stats->generic_iters += (uint32_t)ws->h_counters[CTR_GENERIC];
+        stats->probe_kernel_bytes += spread ? s.blocks * 512ull + s.bytes_off : ws->h_counters[CTR_BYTES];
+        stats->probe_kernel_fetched_bytes += spread ? reads * 128ull : unspread_fetched_bytes(ws, snap);
+        stats->path_flags |= 1u | (Cf ? 2u : 0u) | (pr.used_fused ? 4u : 0u) | (binned ? 8u : 0u) | (ref_docs ? 32u : 0u);
+    }
+    if ((rc = deliver_qstats(b))) return rc;
+    ws->hint_P = b.P; ws->hint_H = std::max<uint64_t>(H, 1);
+    ws->hint_misc = binned ? misc : 0;
     ws->hint_def = 0;
     if (used_lean) for (uint32_t i = 0; i < snap->n_lean; ++i) ws->hint_def = std::max<uint32_t>(ws->hint_def, ws->h_def_count[(size_t)i * DEF_COUNT_STRIDE]);
     return FPX_OK;
 }
 
+// ---- a single /_search (B == 1): latency bound, and every HIP call costs microseconds (and a runtime lock shared with the other host
+//      threads).  Its pipeline runs with fixed sizes, reads its inputs from and writes its outputs to device-mapped pinned memory (no
+//      copy, memset or event calls), synchronises once, and is checked at the end; anything that does not fit falls back to the general path.
+static int run_single(Batch& b, const Keys& keys)
+{
+    Snapshot* snap = b.snap; Workspace* ws = b.ws; hipStream_t st = b.st; int rc;
+    Probes pr;
+    pr.single_fast = true;
+    if ((rc = launch_probes(b, keys, pr))) return rc;
+    if (ws->cap_cands < SINGLE_CANDS && (rc = grow_pair(ws->d_cands, &ws->cap_cands, SINGLE_CANDS))) return rc;
+    static const hipError_t lds_attr1 = hipFuncSetAttribute(reinterpret_cast<const void*>(&k_score<32, true>),
+                                                            hipFuncAttributeMaxDynamicSharedMemorySize, 128 * 1024);
+    (void)lds_attr1;
+    const uint32_t log2f = 13, sb1 = 32u - b.qb;
+    hipLaunchKernelGGL((k_score<32, true>), dim3(1), dim3(WG), ((size_t)8 << SCORE_TABLE_LOG2) + ((size_t)4 << log2f), st,
+                       (const uint64_t*)ws->d_hits[0], (const uint64_t*)nullptr, b.d_opts, log2f | (SCORE_TABLE_LOG2 << 8), sb1, ws->d_cands[0],
+                       (uint64_t)SINGLE_CANDS, ws->d_counters, (uint64_t)ws->cap_hits, (uint64_t*)nullptr, (uint32_t*)nullptr, (uint32_t*)nullptr, b.cancel);
+    if (!ws->d_ret) FPX_HIP(hipHostGetDevicePointer(reinterpret_cast<void**>(&ws->d_ret), ws->h_counters, 0));
+    hipLaunchKernelGGL(k_finish_single, dim3(1), dim3(256), 0, st, (const uint64_t*)ws->d_cands[0], b.d_opts,
+                       (const unsigned long long*)ws->d_counters, b.out_cap, ws->d_ret);
+    FPX_HIP(hipGetLastError());
+    FPX_SYNC_BATCH(b);      // counters, result count and results are in pinned host memory now
+    if (b.timeout_ms && now_ms() - b.t_start > (double)b.timeout_ms) return FPX_E_TIMEOUT;
+    const uint64_t H = ws->h_counters[CTR_HITS];
+    const bool fits = H <= ws->cap_hits && ws->h_counters[CTR_CANDS] <= SINGLE_CANDS && ws->h_counters[CTR_MAXSCORE] == 0;
+    if (!fits) {                           // rare: rerun on the general path (which grows buffers / splits as needed)
+        if (H > ws->cap_hits && (rc = grow_pair(ws->d_hits, &ws->cap_hits, (size_t)H + 1024))) return rc;
+        return FPX_REDO;
+    }
+    *b.out_n = (uint32_t)ws->h_counters[CTR_COUNT];
+    std::memcpy(b.out, ws->h_counters + CTR_COUNT + 1, (size_t)*b.out_n * sizeof(fpx_result));
+    gather_hist(ws->batch_hist, ws->h_counters, nullptr, ws->h_counters[CTR_PROBES]);
+    if (fpx_stats* stats = b.stats) {        // counters only: the fast path takes no device timestamps
+        stats->probes += ws->h_counters[CTR_PROBES]; stats->scanned_blocks += ws->h_counters[CTR_BLOCKS]; stats->scanned_docs += ws->h_counters[CTR_DOCS];
+        stats->hits += H; stats->algorithmic_bytes += ws->h_counters[CTR_BYTES]; stats->candidates += ws->h_counters[CTR_CANDS];
+        stats->probe_launches += pr.launches; stats->generic_iters += (uint32_t)ws->h_counters[CTR_GENERIC];
+        stats->probe_kernel_bytes += ws->h_counters[CTR_BYTES]; stats->probe_kernel_fetched_bytes += unspread_fetched_bytes(ws, snap);
+    }
+    return FPX_OK;
+}
+
+// ---- the general path: every size comes back to the host before the next step is sized; the exchange modes cut it at the hit records
 static void add_stats(fpx_stats* dst, const fpx_stats& s)
 {
     dst->probes += s.probes; dst->scanned_blocks += s.scanned_blocks; dst->scanned_docs += s.scanned_docs;
@@ -1616,6 +1387,245 @@ static void add_stats(fpx_stats* dst, const fpx_stats& s)
     dst->path_flags |= s.path_flags;
 }
 
+// exchange mode 1: group the H records by destination rank (doc & (world - 1)) and hand them to the caller
+static int hand_records_over(Batch& b, const Exchange* ex, uint64_t H)
+{
+    Workspace* ws = b.ws; hipStream_t st = b.st; int rc;
+    const uint32_t world = ex->world, mask = world - 1u;
+    if (world > 1 && H) {
+        int hcur = 0;
+        if ((rc = sort_keys(ws, ws->d_hits, H, 0, bits_for(world), st, &hcur))) return rc;
+        if (hcur != 0) std::swap(ws->d_hits[0], ws->d_hits[1]);
+    }
+    if ((rc = grow(&ws->d_qrange, &ws->cap_qrange, (size_t)world + 2))) return rc;
+    hipLaunchKernelGGL(k_dest_bounds, dim3((world + 1 + 63) / 64), dim3(64), 0, st,
+                       (const uint64_t*)ws->d_hits[0], H, mask, world, ws->d_qrange);
+    FPX_HIP(hipGetLastError());
+    std::vector<uint64_t> hb(world + 1);
+    FPX_HIP(hipMemcpyAsync(hb.data(), ws->d_qrange, ((size_t)world + 1) * sizeof(uint64_t), hipMemcpyDeviceToHost, st));
+    const bool fits = H <= ex->cap;
+    if (fits && H) FPX_HIP(hipMemcpyAsync(ex->d_records, ws->d_hits[0], H * sizeof(uint64_t), hipMemcpyDeviceToDevice, st));
+    FPX_HIP(hipEventRecord(ws->ev_end, st));
+    FPX_SYNC_BATCH(b);
+    for (uint32_t d = 0; d < world; ++d) ex->counts[d] = hb[d + 1] - hb[d];
+    if (!fits) { set_error("records buffer too small: %llu records (counts are filled in; retry with room for them)", (unsigned long long)H); return FPX_E_INVAL; }
+    return FPX_OK;
+}
+
+// ---- 5+6: partition the H hit records by query, count per (query, doc) in LDS, keep score >= min_score; sort the candidates by
+//      (q, score desc, id asc).  *C of them in the shared list d_cands[*ccur]; FPX_SPLIT: a score does not fit the key's `sb` bits
+static int score_general(Batch& b, bool score_only, uint64_t H, uint32_t sb, CandSlots* cs, uint64_t* C_out, int* ccur)
+{
+    Workspace* ws = b.ws; hipStream_t st = b.st; const uint32_t B = b.B; const unsigned qb = b.qb; int rc;
+    // partition of the records by query (order inside a query is irrelevant to the hash-table count)
+    if ((rc = grow(&ws->d_qrange, &ws->cap_qrange, (size_t)B * 2 + 2))) return rc;
+    if (qb) {
+        int hcur = 0;
+        if ((rc = sort_keys(ws, ws->d_hits, H, 32, 32 + qb, st, &hcur))) return rc;
+        if (hcur != 0) std::swap(ws->d_hits[0], ws->d_hits[1]);   // convention: d_hits[0] holds the data
+    }
+    if ((rc = ensure_cand_slots(ws, B, 0, cs))) return rc;
+    hipLaunchKernelGGL(k_bounds, dim3((B + WG - 1) / WG), dim3(WG), 0, st, (const uint64_t*)ws->d_hits[0], H, B, ws->d_qrange, cs->qcand_n);
+    uint32_t log2f, log2t;
+    score_filter_sizes(min_floor(b.offsets, b.opts, B), H, B, &log2f, &log2t);
+    const bool short_queries = H / B <= (uint64_t)WG * 8u;      // the average query fits one 8-row tile
+    const size_t score_lds = ((size_t)8 << log2t) + ((size_t)4 << log2f);
+    uint64_t C = 0;
+    for (int attempt = 0;; ++attempt) {
+        if (attempt > 0) {                    // first attempt: the counters are still zero, k_bounds zeroed the slot counts
+            FPX_HIP(hipMemsetAsync(&ws->d_counters[CTR_CANDS], 0, sizeof(unsigned long long), st));
+            FPX_HIP(hipMemsetAsync(&ws->d_counters[CTR_MAXSCORE], 0, sizeof(unsigned long long), st));
+            FPX_HIP(hipMemsetAsync(&ws->d_counters[CTR_HEAVY], 0, sizeof(unsigned long long), st));
+            FPX_HIP(hipMemsetAsync(cs->qcand_n, 0, (size_t)B * sizeof(uint32_t), st));
+        }
+        if (short_queries) launch_score<8, false>(b, B, score_lds, ws->d_hits[0], log2f | (log2t << 8), sb, *cs);
+        else launch_score<32, false>(b, B, score_lds, ws->d_hits[0], log2f | (log2t << 8), sb, *cs);
+        FPX_HIP(hipGetLastError());
+        FPX_HIP(hipMemcpyAsync(ws->h_counters, ws->d_counters, CTR_COUNT * sizeof(unsigned long long), hipMemcpyDeviceToHost, st));
+        FPX_SYNC_BATCH(b);
+        if (ws->h_counters[CTR_HEAVY] != 0) {
+            // queries the launch above handed over (far more records than the filter was sized for): rounds over doc classes
+            launch_score<32, true>(b, (uint32_t)std::min<uint64_t>(ws->h_counters[CTR_HEAVY], 1024u), score_lds, ws->d_hits[0], log2f | (log2t << 8), sb, *cs);
+            FPX_HIP(hipGetLastError());
+            FPX_HIP(hipMemcpyAsync(ws->h_counters, ws->d_counters, CTR_COUNT * sizeof(unsigned long long), hipMemcpyDeviceToHost, st));
+            FPX_SYNC_BATCH(b);
+        }
+        C = ws->h_counters[CTR_CANDS];
+        if (ws->h_counters[CTR_MAXSCORE] != 0) {              // a score does not fit the key's score field
+            if (B <= 1) { set_error("score overflows u32"); return FPX_E_INVAL; }
+            if (score_only) { set_error("a score does not fit the candidate key: use smaller query batches"); return FPX_E_INVAL; }
+            return FPX_SPLIT;                                  // the caller retries with smaller batches
+        }
+        if (C <= ws->cap_cands) break;
+        if (attempt >= 2) { set_error("candidate buffer overflow persists"); return FPX_E_DEVICE; }
+        if ((rc = grow_pair(ws->d_cands, &ws->cap_cands, (size_t)C + 1024))) return rc;
+    }
+    if (C && (rc = sort_keys(ws, ws->d_cands, C, 0, 64, st, ccur))) return rc;
+    *C_out = C;
+    return FPX_OK;
+}
+
+static int run_general(Batch& b, const Keys& keys, const Exchange* ex)
+{
+    Snapshot* snap = b.snap; Workspace* ws = b.ws; hipStream_t st = b.st; const uint32_t B = b.B; const uint64_t P = b.P;
+    const bool probe_only = ex && ex->mode == 1, score_only = ex && ex->mode == 2;
+    int rc;
+    fpx_stats gs{};                             // this entry's statistics: added to the caller's at the end
+    uint64_t H = 0, C = 0;                      // hit records; candidates in the shared list
+    // ---- 3+4: probes (rerun with a larger hit buffer on overflow)
+    Probes pr;
+    for (pr.attempt = 0;; ++pr.attempt) {
+        if ((rc = launch_probes(b, keys, pr))) return rc;
+        FPX_HIP(hipMemcpyAsync(ws->h_counters, ws->d_counters, CTR_COUNT * sizeof(unsigned long long), hipMemcpyDeviceToHost, st));
+        FPX_SYNC_BATCH(b);
+        if (pr.spread) {
+            // the lean / direct kernels' statistics sets, summed into the slots the code below reads
+            const StatSums s = sum_stat_sets(host_stat_sets(b));
+            ws->h_counters[CTR_LEAN_READS] = s.reads + (s.dreads + 1) / 2;           // (k_probe_direct counts 64-byte requests)
+            ws->h_counters[8 + CTR_BLOCKS] = s.blocks; ws->h_counters[8 + CTR_BYTES] = s.blocks * 512ull + s.bytes_off;
+            ws->h_counters[8 + CTR_DOCS] = s.docs; ws->h_counters[8 + CTR_PROBES] = s.probes;
+        }
+        if (P && (snap->n_file || snap->n_direct)) {
+            float ms = 0.f;
+            FPX_HIP(hipEventElapsedTime(&ms, ws->ev_probe0, ws->ev_probe1));
+            gs.probe_kernel_ms = ms;
+            gs.probe_aux_ms = 0.f;
+            if (pr.used_lean) FPX_HIP(hipEventElapsedTime(&gs.probe_aux_ms, ws->ev_probe1, ws->ev_probe2));
+        }
+        H = ws->h_counters[CTR_HITS];
+        if (pr.used_lean) {
+            bool overflow = false;
+            for (uint32_t i = 0; i < snap->n_lean; ++i) overflow = overflow || ws->h_def_count[(size_t)i * DEF_COUNT_STRIDE] > b.def_cap;
+            if (overflow) {                 // pathological data: nearly every probe needs the generic path
+                if (pr.attempt >= 3) { set_error("deferred list overflow persists"); return FPX_E_DEVICE; }
+                pr.force_generic = true;
+                continue;
+            }
+        }
+        if (H <= ws->cap_hits) break;
+        if (pr.attempt >= 4) { set_error("hit buffer overflow persists (%llu records)", (unsigned long long)H); return FPX_E_DEVICE; }
+        if ((rc = grow_pair(ws->d_hits, &ws->cap_hits, (size_t)H + 1024))) return rc;
+    }
+    const bool spread = pr.spread, used_lean = pr.used_lean;
+    if (score_only) {                           // the records come from the exchange instead of the probes above
+        H = ex->n;
+        if (H > ws->cap_hits && (rc = grow_pair(ws->d_hits, &ws->cap_hits, (size_t)H + 1024))) return rc;
+        if (H) FPX_HIP(hipMemcpyAsync(ws->d_hits[0], ex->d_records, H * sizeof(uint64_t), hipMemcpyDeviceToDevice, st));
+    }
+    if (b.timeout_ms && now_ms() - b.t_start > (double)b.timeout_ms) return FPX_E_TIMEOUT;
+    // statistics: slots 0..7 are written by k_probe (generic / deferred / memory), 8..15 by k_probe_lean8
+    gs.scanned_blocks = ws->h_counters[CTR_BLOCKS] + ws->h_counters[8 + CTR_BLOCKS]; gs.scanned_docs = ws->h_counters[CTR_DOCS] + ws->h_counters[8 + CTR_DOCS];
+    gs.algorithmic_bytes = ws->h_counters[CTR_BYTES] + ws->h_counters[8 + CTR_BYTES]; gs.probes = ws->h_counters[CTR_PROBES] + ws->h_counters[8 + CTR_PROBES];
+    gs.generic_iters = (uint32_t)ws->h_counters[CTR_GENERIC];
+    gs.probe_kernel_bytes = spread ? ws->h_counters[8 + CTR_BYTES] : ws->h_counters[CTR_BYTES];
+    gs.probe_kernel_fetched_bytes = spread ? ws->h_counters[CTR_LEAN_READS] * 128ull /* (lines) */ : unspread_fetched_bytes(ws, snap);
+    gs.hits = H; gs.probe_launches = pr.launches; gs.path_flags = pr.used_fused ? 4u : 0u;
+    if (!score_only) gather_hist(ws->batch_hist, ws->h_counters, spread ? host_stat_sets(b) : nullptr, gs.probes);
+    auto fill_stats = [&]() {
+        if (!b.stats) return;
+        (void)hipEventElapsedTime(&gs.total_gpu_ms, ws->ev_begin, ws->ev_end);
+        add_stats(b.stats, gs);
+    };
+    if (probe_only) {
+        if ((rc = hand_records_over(b, ex, H))) return rc;
+        fill_stats();
+        return FPX_OK;
+    }
+    int ccur = 0;
+    const uint32_t sb = 32u - b.qb;             // score field of the candidate key; larger scores -> split the batch
+    CandSlots cs;                               // (no records: no slots, and k_finish looks at none)
+    if (H && (rc = score_general(b, score_only, H, sb, &cs, &C, &ccur))) return rc;
+    if (b.timeout_ms && now_ms() - b.t_start > (double)b.timeout_ms) return FPX_E_TIMEOUT;
+
+    // ---- finish
+    const bool count_slots = b.stats && cs.qcand_n;
+    launch_finish(b, ws->d_cands[ccur], C, sb, cs, b.partial ? b.out : ws->d_out, b.partial ? b.out_n : ws->d_out_n, count_slots);
+    FPX_HIP(hipGetLastError());
+    bool staged = false;
+    if (!b.partial && (rc = stage_results(ws, B, b.out_cap, st, &staged))) return rc;
+    if (count_slots)
+        FPX_HIP(hipMemcpyAsync(&ws->h_counters[CTR_SLOTCANDS], &ws->d_counters[CTR_SLOTCANDS], sizeof(unsigned long long), hipMemcpyDeviceToHost, st));
+    FPX_HIP(hipEventRecord(ws->ev_end, st));
+    FPX_SYNC_BATCH(b);
+    if (b.timeout_ms && now_ms() - b.t_start > (double)b.timeout_ms) return FPX_E_TIMEOUT;
+    if (!b.partial && (rc = deliver_results(ws, B, b.out_cap, staged, b.out, b.out_n, st))) return rc;
+    gs.candidates = C + (count_slots ? ws->h_counters[CTR_SLOTCANDS] : 0ull);       // (in the shared list + in the queries' own slots)
+    fill_stats();
+    if ((rc = deliver_qstats(b))) return rc;
+    ws->hint_P = P; ws->hint_H = std::max<uint64_t>(H, 1);       // sizes the device-sized path of the next batch
+    ws->hint_def = 0;
+    if (used_lean) for (uint32_t i = 0; i < snap->n_lean; ++i) ws->hint_def = std::max<uint32_t>(ws->hint_def, ws->h_def_count[(size_t)i * DEF_COUNT_STRIDE]);
+    return FPX_OK;
+}
+
+// ---- one batch, one path: fill the Batch, choose, call the path's driver.  FPX_REDO_QS and FPX_REDO may escape to the caller: a caller
+//      without an Exchange (the only ones whose batches take the paths that raise them) goes through run_with_redos, which re-enters.
+static int run_batch(Snapshot* snap, Workspace* ws, const QueryBatch* resident, uint32_t q0,
+                     const uint32_t* hashes, const uint64_t* offsets, uint32_t B,
+                     const fpx_opts* opts, uint32_t timeout_ms, bool partial,
+                     fpx_result* out, uint32_t out_cap, uint32_t* out_n, fpx_stats* stats, const Exchange* ex = nullptr,
+                     Try mode = Try::First, double t_call = 0.0, uint64_t* q_blocks = nullptr, uint64_t* q_docs = nullptr)
+{
+    const bool score_only = ex && ex->mode == 2;
+    const bool no_fast = mode == Try::GeneralOnly, no_qs = mode != Try::First;
+    Batch b{};
+    b.snap = snap; b.ws = ws; b.st = ws->stream;
+    b.resident = resident; b.q0 = q0; b.hashes = hashes; b.offsets = offsets; b.opts = opts; b.B = B;
+    // the deadline counts from the API call's entry (one deadline per search, src/MultiIndex.zig:314-322), however often the
+    // batch re-enters here (a redo on the general path, the two halves of a split)
+    b.t_start = t_call != 0.0 ? t_call : now_ms(); b.timeout_ms = timeout_ms;
+    std::memset(ws->batch_hist, 0, sizeof ws->batch_hist);
+    __atomic_store_n(ws->h_cancel, 0u, __ATOMIC_RELEASE);           // (the stream is idle: the previous call synchronised it)
+    b.cancel = timeout_ms ? ws->d_cancel : nullptr;
+    b.base = offsets[0]; b.P = offsets[B] - b.base; b.qb = bits_for(B);                         // (q in [0, B))
+    b.partial = partial; b.out = out; b.out_cap = out_cap; b.out_n = out_n; b.stats = stats; b.q_blocks = q_blocks; b.q_docs = q_docs;
+    const uint64_t P = b.P;
+    int rc;
+    if ((rc = ensure_queries(ws, B))) return rc;       // d_out_n (+ staging for non-resident batches)
+    if ((rc = grow_pair(ws->d_keys, &ws->cap_keys, (size_t)P + 1))) return rc;
+    if (!partial && (rc = grow(&ws->d_out, &ws->cap_out, (size_t)B * out_cap + 1))) return rc;
+    static_assert(sizeof(fpx_result) == 8, "fpx_result layout");
+
+    // ---- the path.  A: a query per workgroup, where the snapshot and the queries suit k_search_query or k_search_side (a snapshot has one
+    //      group or none: never both); B: the pipeline -- for one query its single-launch form, else device-sized (below) or general
+    const bool single_fast = B == 1 && !partial && !ex && !no_fast && P != 0 && out_cap <= SINGLE_OUT_MAX &&
+                             (snap->n_lean == 0 || P * snap->n_file < lean_min_probes(snap->ctx));
+    bool query_wg = false, side_wg = false, filt = false;
+    if (!ex && !no_fast && !no_qs && !single_fast && B >= 2u && P != 0 && b.qb <= 24u) {
+        query_wg = takes_query_wg(snap, offsets, opts, B, &filt);
+        side_wg = !query_wg && takes_side_wg(snap, offsets, opts, B);
+        if (query_wg || side_wg) {
+            // (after a batch that was handed back: the next ones do not try again at once -- hot-hash traffic comes in runs; the
+            // snapshot's own count -- a part 1 is a snapshot of its own)
+            const uint32_t skip = __atomic_load_n(&snap->qs_skip, __ATOMIC_RELAXED);
+            if (skip != 0u) { __atomic_store_n(&snap->qs_skip, skip - 1u, __ATOMIC_RELAXED); query_wg = side_wg = false; }
+        }
+    }
+
+    if (!single_fast) FPX_HIP(hipEventRecord(ws->ev_begin, b.st));
+    if ((rc = place_batch(b, query_wg))) return rc;
+    if ((rc = ensure_def_lists(b, side_wg))) return rc;
+    // (every memset is a 5-us launch of its own: the batch's zeroing rides in kernels that run anyway where it can)
+    Keys keys{};
+    if (!query_wg && !side_wg && (rc = make_keys(b, single_fast, score_only, &keys))) return rc;
+    // per-query scan statistics, when the caller asked for them (a single query's are the call's totals: search_split)
+    b.want_q = (q_blocks || q_docs) && B >= 2u && !score_only;
+    if (b.want_q && (rc = grow(&ws->d_qstats, &ws->cap_qstats, (size_t)B + 1))) return rc;
+    if (query_wg) return run_query_wg(b, filt);
+    if (side_wg) return run_side_wg(b);
+
+    if (ws->cap_hits == 0) {
+        size_t want = std::max<size_t>(1u << 20, (size_t)P * std::max<uint32_t>(1u, snap->n_file + snap->n_direct + snap->n_mem));
+        if ((rc = grow_pair(ws->d_hits, &ws->cap_hits, want))) return rc;
+    }
+    bool fast = ctx_opt(snap->ctx, OPT_FAST) != 0 && !ex && !no_fast && !single_fast && B >= 2u && P != 0 && b.qb <= 24u &&
+                (1u << level1_bits(b.qb)) <= MAX_BINS && ws->hint_H != 0 && ws->hint_P != 0;
+    if (fast && ws->fast_penalty != 0) { ws->fast_penalty -= 1; fast = false; }
+    if (fast) return run_device_sized(b, keys);
+    if (single_fast) return run_single(b, keys);
+    return run_general(b, keys, ex);
+}
+
 // one pass, or -- when (query index, score) do not fit the 64-bit candidate key -- two half batches
 // would part 0 of the snapshot run this batch a query per workgroup?  (run_batch's own test for it, on the host arrays; a batch it would
 // not take gains nothing from two parts.  A part 0 whose group has superseded docs or masked columns -- made under query_wg 2 -- only
@@ -1624,16 +1634,9 @@ static bool parts_take(const Snapshot* snap, const uint64_t* offsets, const fpx_
 {
     const int64_t query_wg = ctx_opt(snap->ctx, OPT_QUERY_WG);
     if (query_wg == 0) return false;
-    if (query_wg != 2) {
-        const GroupDesc& gd = snap->part[0]->h_group[0];
-        if (gd.any_dead != 0u || gd.active != (gd.nseg >= 32u ? 0xFFFFFFFFu : ((1u << gd.nseg) - 1u))) return false;
-    }
+    if (query_wg != 2 && group_filtered(snap->part[0]->h_group[0])) return false;
     if (bits_for(B) > 24u || offsets[B] == offsets[0]) return false;
-    for (uint32_t q = 0; q < B; ++q) {
-        const uint64_t raw_len = offsets[q + 1] - offsets[q];
-        if (raw_len > QS_MAX_HASHES || (opts[q].has_min_score ? opts[q].min_score : (uint32_t)((raw_len + 19) / 20)) <= 2u) return false;
-    }
-    return true;
+    return queries_fit_wg(offsets, opts, B);
 }
 
 // one batch on one workspace, redone where a path hands it back; FPX_OK, FPX_SPLIT (the caller halves the batch) or an error
@@ -1641,14 +1644,15 @@ static int run_with_redos(Snapshot* snap, Workspace* ws, const QueryBatch* resid
                           const fpx_opts* opts, uint32_t timeout_ms, bool partial, fpx_result* out, uint32_t out_cap, uint32_t* out_n, fpx_stats* local,
                           double t_call, uint64_t* q_blocks, uint64_t* q_docs)
 {
-    int rc = run_batch(snap, ws, resident, q0, hashes, offsets, B, opts, timeout_ms, partial, out, out_cap, out_n, local, nullptr, false, t_call, q_blocks, q_docs);
+    auto run = [&](Try mode) { return run_batch(snap, ws, resident, q0, hashes, offsets, B, opts, timeout_ms, partial, out, out_cap, out_n, local, nullptr, mode, t_call, q_blocks, q_docs); };
+    int rc = run(Try::First);
     if (rc == FPX_REDO_QS) {                    // the one-workgroup-per-query path handed the batch back: the pipeline
         *local = fpx_stats{};
-        rc = run_batch(snap, ws, resident, q0, hashes, offsets, B, opts, timeout_ms, partial, out, out_cap, out_n, local, nullptr, false, t_call, q_blocks, q_docs, true);
+        rc = run(Try::NoQueryWg);
     }
-    if (rc == FPX_REDO) {                       // the device-sized path gave up (after its synchronisation): the general path
+    if (rc == FPX_REDO) {                       // the device-sized or the single-query path gave up (after its synchronisation): the general path
         *local = fpx_stats{};
-        rc = run_batch(snap, ws, resident, q0, hashes, offsets, B, opts, timeout_ms, partial, out, out_cap, out_n, local, nullptr, true, t_call, q_blocks, q_docs);
+        rc = run(Try::GeneralOnly);
     }
     return rc;
 }
@@ -2053,7 +2057,7 @@ int shard_probe_impl(Snapshot* snap, const QueryBatch* qb, uint32_t world, uint3
     // one-GPU path hands such batches to k_score's count-only round, run_batch's `binned`; here the record protocol takes them)
     for (uint32_t q = 0; q < B; ++q) {
         const fpx_opts& o = qb->opts[q];
-        if ((o.has_min_score ? o.min_score : (uint32_t)((offsets[q + 1] - offsets[q] + 19) / 20)) <= 2u) {
+        if (query_floor(o, offsets[q + 1] - offsets[q]) <= 2u) {
             set_error("fpx_shard_probe: query %u has a score floor of 1 or 2: this batch takes the record protocol (fpx_probe_resident)", q); return FPX_E_INVAL;
         }
     }
@@ -2177,18 +2181,14 @@ int shard_probe_impl(Snapshot* snap, const QueryBatch* qb, uint32_t world, uint3
         }
         {   // the window's probes join the context's running scan histograms (a step the ranks redo for larger buffers is observed again)
             const unsigned long long* ls = reinterpret_cast<const unsigned long long*>(ws->h_cells);
-            unsigned long long probes = 0;
-            for (uint32_t i = 0; i < LEAN_STAT_SETS; ++i) probes += ls[i * 8 + 3];
             uint64_t hist[HIST_SLOTS + 1];
-            gather_hist(hist, ws->h_counters, ls, probes);
+            gather_hist(hist, ws->h_counters, ls, sum_stat_sets(ls).probes);
             ctx_hist_add(snap->ctx, hist, hist[HIST_SLOTS]);
         }
         if (stats) {
-            const unsigned long long* ls = reinterpret_cast<const unsigned long long*>(ws->h_cells);
-            unsigned long long blocks = 0, docs = 0, probes = 0, dreads = 0;
-            unsigned long long bytes_off = 0;
-            unsigned long long pads = ws->h_counters[CTR_PADS];
-            for (uint32_t i = 0; i < LEAN_STAT_SETS; ++i) { blocks += ls[i * 8 + 1]; docs += ls[i * 8 + 2]; probes += ls[i * 8 + 3]; dreads += ls[i * 8 + 4]; bytes_off += ls[i * 8 + 5]; pads += ls[i * 8 + 6]; }
+            const StatSums s = sum_stat_sets(reinterpret_cast<const unsigned long long*>(ws->h_cells));
+            const unsigned long long blocks = s.blocks, docs = s.docs, probes = s.probes, dreads = s.dreads, bytes_off = s.bytes_off;
+            const unsigned long long pads = ws->h_counters[CTR_PADS] + s.pads;
             float ms = 0.f;
             (void)hipEventElapsedTime(&ms, ws->ev_probe0, ws->ev_probe1);
             stats->probes = probes; stats->scanned_blocks = blocks; stats->scanned_docs = docs; stats->hits = ws->h_counters[CTR_SLOTCANDS] - std::min<unsigned long long>(pads, ws->h_counters[CTR_SLOTCANDS]);
@@ -2230,7 +2230,7 @@ int shard_keys_impl(Ctx* ctx, const QueryBatch* qb, uint32_t world, uint32_t ran
         const uint64_t len = offsets[q + 1] - offsets[q];
         if (len > DEDUP_MAX) { set_error("fpx_shard_keys: queries of more than %u hashes (use fpx_probe_resident)", DEDUP_MAX); return FPX_E_INVAL; }
         const fpx_opts& o = qb->opts[q];
-        if ((o.has_min_score ? o.min_score : (uint32_t)((len + 19) / 20)) <= 2u) {
+        if (query_floor(o, len) <= 2u) {
             set_error("fpx_shard_keys: query %u has a score floor of 1 or 2: this batch takes the record protocol (fpx_probe_resident)", q_lo + q); return FPX_E_INVAL;
         }
     }
@@ -2366,18 +2366,14 @@ int shard_probe_keys_impl(Snapshot* snap, const uint64_t* d_keys_recv, uint64_t 
         }
         {   // the window's probes join the context's running scan histograms (a step the ranks redo for larger buffers is observed again)
             const unsigned long long* ls = reinterpret_cast<const unsigned long long*>(ws->h_cells);
-            unsigned long long probes = 0;
-            for (uint32_t i = 0; i < LEAN_STAT_SETS; ++i) probes += ls[i * 8 + 3];
             uint64_t hist[HIST_SLOTS + 1];
-            gather_hist(hist, ws->h_counters, ls, probes);
+            gather_hist(hist, ws->h_counters, ls, sum_stat_sets(ls).probes);
             ctx_hist_add(snap->ctx, hist, hist[HIST_SLOTS]);
         }
         if (stats) {
-            const unsigned long long* ls = reinterpret_cast<const unsigned long long*>(ws->h_cells);
-            unsigned long long blocks = 0, docs = 0, probes = 0, dreads = 0;
-            unsigned long long bytes_off = 0;
-            unsigned long long pads = ws->h_counters[CTR_PADS];
-            for (uint32_t i = 0; i < LEAN_STAT_SETS; ++i) { blocks += ls[i * 8 + 1]; docs += ls[i * 8 + 2]; probes += ls[i * 8 + 3]; dreads += ls[i * 8 + 4]; bytes_off += ls[i * 8 + 5]; pads += ls[i * 8 + 6]; }
+            const StatSums s = sum_stat_sets(reinterpret_cast<const unsigned long long*>(ws->h_cells));
+            const unsigned long long blocks = s.blocks, docs = s.docs, probes = s.probes, dreads = s.dreads, bytes_off = s.bytes_off;
+            const unsigned long long pads = ws->h_counters[CTR_PADS] + s.pads;
             float ms = 0.f;
             (void)hipEventElapsedTime(&ms, ws->ev_probe0, ws->ev_probe1);
             stats->probes = probes; stats->scanned_blocks = blocks; stats->scanned_docs = docs; stats->hits = ws->h_counters[CTR_SLOTCANDS] - std::min<unsigned long long>(pads, ws->h_counters[CTR_SLOTCANDS]);
@@ -2494,9 +2490,7 @@ int shard_score_impl(Ctx* ctx, const QueryBatch* qb, uint32_t world, uint32_t ra
         if (ws->h_counters[CTR_CANDS] != 0) {             // queries with more candidates than slots: sort the shared list, finish again
             const uint64_t Cf = ws->h_counters[CTR_CANDS];
             int ccur = 0;
-            const size_t tb2 = sort_u64_temp_bytes(Cf, 0, 64);
-            if ((rc = grow(reinterpret_cast<uint8_t**>(&ws->d_temp), &ws->cap_temp, tb2 + 256))) return rc;
-            FPX_HIP(sort_u64(ws->d_temp, ws->cap_temp, ws->d_cands[0], ws->d_cands[1], Cf, 0, 64, st, &ccur));
+            if ((rc = sort_keys(ws, ws->d_cands, Cf, 0, 64, st, &ccur))) return rc;
             finish(ws->d_cands[ccur], Cf);
             FPX_HIP(hipGetLastError());
             if ((rc = stage_results(ws, nq, out_cap, st, &staged))) return rc;
