@@ -423,6 +423,7 @@ static const OptInfo OPT_TABLE[OPT_COUNT] = {
     /* OPT_QUERY_WG */           {"query_wg", "FPX_QUERY_WG", 1, 0, false},                      // 1 | 0 | 2: a snapshot that is ONE packed group is searched a query per workgroup (fpx_qsearch.hpp) | by the keys - probe - bins - score pipeline | as 1, a group with superseded docs or masked columns too
     /* OPT_SIDE_WG */            {"side_wg", "FPX_SIDE_WG", 0, 0, false},                        // 0 | 1: the file segments next to the group (small decoded, direct-addressed alone) by the pipeline | a query per workgroup (fpx_qside.hpp)
     /* OPT_HOT_WG */             {"hot_wg", "FPX_HOT_WG", 0, 0, false},                          // 0 | 1: a query whose records outgrow k_search_query's LDS array hands the batch to the pipeline | is redone in doc classes by k_search_classes (fpx_qsearch.hpp; unfiltered only)
+    /* OPT_WORDS_WG */           {"words_wg", "FPX_WORDS_WG", 0, 0, false},                      // 0 | 1 | 2: a snapshot that is ONE group in directory + words form by the pipeline | a query per workgroup (fpx_qwords.hpp) | as 1, a group with superseded docs or masked columns too
 };
 
 int64_t ctx_opt(const Ctx* c, CtxOpt o)
@@ -1042,6 +1043,19 @@ int fpx_snapshot_create(fpx_ctx* ctx_, fpx_segment* const* segs, uint32_t num_se
             const Group* g = sn->groups[gi].get();
             if (!g->packed) continue;
             if (query_wg != 2 && (gd.any_dead != 0u || gd.active != (gd.nseg >= 32u ? 0xFFFFFFFFu : ((1u << gd.nseg) - 1u)))) continue;
+            uint64_t items = 0;
+            for (const Segment* s : sn->segs) if (s->kind == 0 && s->ctx == c && s->home == sn->groups[gi]) items += s->num_items;
+            if (g0 < 0 || items > g0_items) { g0 = (int)gi; g0_items = items; }
+        }
+    }
+    // No packed group for part 0, and option words_wg -- the value in force now -- is set: the largest group in DIRECTORY + WORDS form that
+    // is whole here (k_search_words, fpx_qwords.hpp; under words_wg 2 one with superseded docs or columns outside the snapshot too).
+    const int64_t words_wg = ctx_opt(c, OPT_WORDS_WG);
+    if (g0 < 0 && words_wg != 0 && (sn->n_file != 0 || sn->n_solo != 0 || sn->n_group > 1)) {
+        for (uint32_t gi = 0; gi < sn->n_group; ++gi) {
+            const GroupDesc& gd = sn->h_group[gi];
+            if (sn->groups[gi]->packed) continue;
+            if (words_wg != 2 && (gd.any_dead != 0u || gd.active != (gd.nseg >= 32u ? 0xFFFFFFFFu : ((1u << gd.nseg) - 1u)))) continue;
             uint64_t items = 0;
             for (const Segment* s : sn->segs) if (s->kind == 0 && s->ctx == c && s->home == sn->groups[gi]) items += s->num_items;
             if (g0 < 0 || items > g0_items) { g0 = (int)gi; g0_items = items; }

@@ -10,7 +10,8 @@
 // GPU formulation (a batch of B queries at once) -- two of them, chosen per batch by run_batch, which fills a Batch and calls one driver:
 //   A. a snapshot that is ONE packed group (the resident index between merges): k_search_query (fpx_qsearch.hpp), a QUERY PER WORKGROUP --
 //      dedup, the group's lines, counting and the floor in one kernel, the hit records never leaving the CU -- then k_finish, k_publish
-//      (run_query_wg; run_side_wg for the file segments next to the group).
+//      (run_query_wg; run_side_wg for the file segments next to the group; run_words_wg -- option words_wg, k_search_words in
+//      fpx_qwords.hpp -- for a snapshot that is one group in directory + words form).
 //   B. everything else, the pipeline over all the batch's hashes (make_keys, launch_probes; run_device_sized, run_single or run_general):
 //      1. k_make_keys*     (hash, q) keys, packed hash << QB | q; ordered by hash bucket (fpx_keyorder.hpp / fpx_sort.hip) or per query in LDS:
 //                          duplicates become adjacent (dedupSorted) and neighbouring probes walk neighbouring lines
@@ -46,6 +47,7 @@
 #include "fpx_score_bin.hpp"
 #include "fpx_qsearch.hpp"
 #include "fpx_qside.hpp"
+#include "fpx_qwords.hpp"
 
 namespace fpx {
 
@@ -708,6 +710,16 @@ static bool takes_side_wg(const Snapshot* snap, const uint64_t* offsets, const f
     for (const SegDesc& d : snap->h_direct) if (!(d.own_flags == 0u && d.drec && d.primary)) return false;
     return queries_fit_wg(offsets, opts, B);
 }
+// ... and for a snapshot that is ONE group in DIRECTORY + WORDS form (fpx_qwords.hpp; option words_wg = 1, 2 for a group with superseded
+// docs or columns outside the snapshot too: *filt).  A window-sliced group may be taken: the kernel honours win_lo / win_hi.
+static bool takes_words_wg(const Snapshot* snap, const uint64_t* offsets, const fpx_opts* opts, uint32_t B, bool* filt)
+{
+    const int64_t words_wg = ctx_opt(snap->ctx, OPT_WORDS_WG);
+    if (!(words_wg != 0 && snap->n_group == 1 && !snap->groups[0]->packed && snap->n_file == 0 && snap->n_solo == 0 && snap->n_direct != 0 &&
+          (snap->n_mem == 0 || snap->mem_items == 0 || snap->d_memtab != nullptr))) return false;
+    *filt = group_filtered(snap->h_group[0]);
+    return (!*filt || words_wg == 2) && queries_fit_wg(offsets, opts, B);
+}
 
 // ---- A. a query per workgroup --------------------------------------------------------------------------------------------------------
 // k_search_query's instantiations: columns of a directory line (8 | 16), per-query scan statistics, the memory segments' table, filtered
@@ -876,6 +888,50 @@ static int run_side_wg(Batch& b)
     const uint64_t Cf = ws->h_counters[CTR_CANDS];
     if (Cf != 0 && (rc = finish_crowded(b, sbf, cs, to, Cf))) return rc;
     return finish_wg_path(b, to, Cf, 512u);
+}
+
+// k_search_words' instantiations: columns of a directory line (8 | 16), the memory segments' table, filtered
+static void launch_search_words(bool ns8, bool mem, bool filt, dim3 grid, hipStream_t st, const WordsArgs& wa, const GroupArgs& g)
+{
+#define FPX_LW(NS, MEM, FILT) hipLaunchKernelGGL((k_search_words<NS, MEM, FILT>), grid, dim3(WORDS_WG), WORDS_LDS_BYTES, st, wa, g)
+#define FPX_LW_MEM(NS, FILT) do { if (mem) FPX_LW(NS, true, FILT); else FPX_LW(NS, false, FILT); } while (0)
+#define FPX_LW_NS(FILT) do { if (ns8) FPX_LW_MEM(8, FILT); else FPX_LW_MEM(16, FILT); } while (0)
+    if (filt) FPX_LW_NS(true); else FPX_LW_NS(false);
+#undef FPX_LW_NS
+#undef FPX_LW_MEM
+#undef FPX_LW
+}
+// ... and a group in directory + words form, by k_search_words (the memory segments behind their table with it)
+static int run_words_wg(Batch& b, bool filt)
+{
+    Snapshot* snap = b.snap; Workspace* ws = b.ws; hipStream_t st = b.st; const uint32_t B = b.B; int rc;
+    CandSlots cs;
+    if ((rc = ensure_cand_slots(ws, B, 0, &cs))) return rc;
+    const uint32_t sbf = 32u - b.qb;
+    hipLaunchKernelGGL(k_qs_zero, dim3(8), dim3(256), 0, st, ws->d_counters, ws->d_def_count, (uint32_t)b.def_words);
+    FPX_HIP(hipEventRecord(ws->ev_probe0, st));
+    WordsArgs wa{};
+    wa.hashes_base = b.d_hashes_base; wa.offsets = b.d_offsets; wa.opts = b.d_opts; wa.B = B; wa.sb = sbf;
+    wa.cands = ws->d_cands[0]; wa.cand_cap = ws->cap_cands; wa.qcand = cs.qcand; wa.qcand_n = cs.qcand_n;
+    wa.counters = ws->d_counters; wa.stat_sets = device_stat_sets(b);
+    wa.qstats = b.want_q ? ws->d_qstats : nullptr; wa.cancel = b.cancel;
+    if (snap->n_mem != 0 && snap->mem_items != 0) { wa.mem_tab = snap->d_memtab; wa.mem_bucket = snap->d_membucket; wa.mem_bits = snap->d_membits; }
+    const GroupArgs gargs{snap->h_group[0], snap->d_direct};
+    // as many workgroups as the chip holds at once (LDS: WORDS_WGS_PER_CU per CU); each takes every gridDim.x-th query
+    const int cus = device_cus(snap->ctx);
+    launch_search_words(snap->groups[0]->ns == 8u, wa.mem_tab != nullptr, filt, dim3(std::min<uint32_t>(B, (uint32_t)cus * WORDS_WGS_PER_CU)), st, wa, gargs);
+    FPX_HIP(hipGetLastError());
+    FPX_HIP(hipEventRecord(ws->ev_probe1, st));
+    ResultsTo to;
+    if ((rc = results_target(b, &to))) return rc;
+    launch_finish(b, ws->d_cands[0], 0, sbf, cs, to.res, to.n, b.stats != nullptr);
+    if ((rc = publish(b, true))) return rc;
+    FPX_HIP(hipEventRecord(ws->ev_end, st));
+    FPX_SYNC_BATCH(b);
+    if (handed_back(ws, snap)) return FPX_REDO_QS;           // (run_with_redos: the pipeline)
+    const uint64_t Cf = ws->h_counters[CTR_CANDS];
+    if (Cf != 0 && (rc = finish_crowded(b, sbf, cs, to, Cf))) return rc;
+    return finish_wg_path(b, to, Cf, 4u | 2048u | (filt ? 256u : 0u));
 }
 
 // ---- B. the pipeline: steps of its three drivers ----------------------------------------------------------------------------------------
@@ -1587,18 +1643,19 @@ static int run_batch(Snapshot* snap, Workspace* ws, const QueryBatch* resident, 
     static_assert(sizeof(fpx_result) == 8, "fpx_result layout");
 
     // ---- the path.  A: a query per workgroup, where the snapshot and the queries suit k_search_query or k_search_side (a snapshot has one
-    //      group or none: never both); B: the pipeline -- for one query its single-launch form, else device-sized (below) or general
+    //      group or none: never both) or, under option words_wg, k_search_words; B: the pipeline -- for one query its single-launch form, else device-sized (below) or general
     const bool single_fast = B == 1 && !partial && !ex && !no_fast && P != 0 && out_cap <= SINGLE_OUT_MAX &&
                              (snap->n_lean == 0 || P * snap->n_file < lean_min_probes(snap->ctx));
-    bool query_wg = false, side_wg = false, filt = false;
+    bool query_wg = false, words_wg = false, side_wg = false, filt = false;
     if (!ex && !no_fast && !no_qs && !single_fast && B >= 2u && P != 0 && b.qb <= 24u) {
         query_wg = takes_query_wg(snap, offsets, opts, B, &filt);
-        side_wg = !query_wg && takes_side_wg(snap, offsets, opts, B);
-        if (query_wg || side_wg) {
+        words_wg = !query_wg && takes_words_wg(snap, offsets, opts, B, &filt);
+        side_wg = !query_wg && !words_wg && takes_side_wg(snap, offsets, opts, B);
+        if (query_wg || words_wg || side_wg) {
             // (after a batch that was handed back: the next ones do not try again at once -- hot-hash traffic comes in runs; the
             // snapshot's own count -- a part 1 is a snapshot of its own)
             const uint32_t skip = __atomic_load_n(&snap->qs_skip, __ATOMIC_RELAXED);
-            if (skip != 0u) { __atomic_store_n(&snap->qs_skip, skip - 1u, __ATOMIC_RELAXED); query_wg = side_wg = false; }
+            if (skip != 0u) { __atomic_store_n(&snap->qs_skip, skip - 1u, __ATOMIC_RELAXED); query_wg = words_wg = side_wg = false; }
         }
     }
 
@@ -1607,11 +1664,12 @@ static int run_batch(Snapshot* snap, Workspace* ws, const QueryBatch* resident, 
     if ((rc = ensure_def_lists(b, side_wg))) return rc;
     // (every memset is a 5-us launch of its own: the batch's zeroing rides in kernels that run anyway where it can)
     Keys keys{};
-    if (!query_wg && !side_wg && (rc = make_keys(b, single_fast, score_only, &keys))) return rc;
+    if (!query_wg && !words_wg && !side_wg && (rc = make_keys(b, single_fast, score_only, &keys))) return rc;
     // per-query scan statistics, when the caller asked for them (a single query's are the call's totals: search_split)
     b.want_q = (q_blocks || q_docs) && B >= 2u && !score_only;
     if (b.want_q && (rc = grow(&ws->d_qstats, &ws->cap_qstats, (size_t)B + 1))) return rc;
     if (query_wg) return run_query_wg(b, filt);
+    if (words_wg) return run_words_wg(b, filt);
     if (side_wg) return run_side_wg(b);
 
     if (ws->cap_hits == 0) {
@@ -1632,7 +1690,8 @@ static int run_batch(Snapshot* snap, Workspace* ws, const QueryBatch* resident, 
 // while the option is 2)
 static bool parts_take(const Snapshot* snap, const uint64_t* offsets, const fpx_opts* opts, uint32_t B)
 {
-    const int64_t query_wg = ctx_opt(snap->ctx, OPT_QUERY_WG);
+    // (a part 0 in directory + words form -- made under words_wg -- while THAT option allows it)
+    const int64_t query_wg = ctx_opt(snap->ctx, snap->part[0]->groups[0]->packed ? OPT_QUERY_WG : OPT_WORDS_WG);
     if (query_wg == 0) return false;
     if (query_wg != 2 && group_filtered(snap->part[0]->h_group[0])) return false;
     if (bits_for(B) > 24u || offsets[B] == offsets[0]) return false;

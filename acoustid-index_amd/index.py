@@ -58,7 +58,10 @@ class Context:
         masked columns too (Stats.path_flags bit 8).  'side_wg': 0 | 1 -- the file segments next to the group (small decoded, direct-addressed
         alone) searched by the pipeline | a query per workgroup (Stats.path_flags bit 9).  'hot_wg': 0 | 1 -- a query whose hit records
         outgrow the query-per-workgroup kernel's array hands the batch to the pipeline | is redone in doc classes, the batch staying on
-        that path (Stats.path_flags bit 10)"""
+        that path (Stats.path_flags bit 10).  'words_wg': 0 | 1 | 2 -- a snapshot that is one group in directory + words form (every group
+        that is not packed) searched by the pipeline | a query per workgroup (Stats.path_flags bit 11) | as 1, a group with superseded
+        docs or masked columns too (bits 11 and 8); read when a snapshot is made as well: part 0 of a snapshot in two parts may then be
+        such a group"""
         check(lib().fpx_ctx_set_option(self.h, name.encode(), int(value)))
 
     def trim(self):

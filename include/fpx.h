@@ -89,7 +89,10 @@ typedef struct {
                                    bit 9: the batch (or its part 1) ran k_search_side: the file segments next to the group -- small decoded
                                    ones, direct-addressed ones on their own -- searched a query per workgroup ("side_wg" 1),
                                    bit 10: some queries of the batch (or of its part 0) were redone in doc classes by k_search_classes:
-                                   their hit records outgrew k_search_query's array, the batch stayed on that path ("hot_wg" 1) */
+                                   their hit records outgrew k_search_query's array, the batch stayed on that path ("hot_wg" 1),
+                                   bit 11: the batch (or its part 0) ran k_search_words: ONE group in directory + words form searched a
+                                   query per workgroup ("words_wg" 1 | 2; bit 2 is set with it, bit 8 when its filtered form ran, bit 6
+                                   -- k_search_query's -- is not) */
     uint64_t probe_kernel_fetched_bytes; /* block bytes the main probe kernel really fetched, in 128-byte lines: a probe
                                    whose hash the segment's presence bits know to be absent counts as a visited block (as in
                                    the reference) without the block being read, and a block that is read costs two lines up
@@ -133,6 +136,16 @@ int  fpx_ctx_device(const fpx_ctx *ctx);     /* the HIP ordinal the context live
  *                        fpx_stats.path_flags bit 10).  Unfiltered snapshots only ("query_wg" 2's filtered form keeps the hand-back);
  *                        a batch with more such queries than max(4, B / 8), or a query that needs more than 32 classes, is
  *                        handed back as under 0
+ *   "words_wg"           0 | 1 | 2   a snapshot that is ONE group in DIRECTORY + WORDS form (every group that is not packed: an index of a
+ *                        few thousand to some 25 M fingerprints, any index with a doc-id span of 2^31 or more) and nothing else, every
+ *                        column searched and no doc superseded, is searched by the pipeline below (default 0) | a QUERY PER WORKGROUP
+ *                        (csrc/fpx_qwords.hpp; fpx_stats.path_flags bit 11), for batches of queries k_search_query would take (up to
+ *                        4096 hashes, a floor above 2) | as 1, and so is a group with superseded docs and/or columns outside the
+ *                        snapshot, by the kernel's filtered form (bits 11 and 8).  Independent of "query_wg", which concerns packed
+ *                        groups.  A query whose records outgrow the workgroup's array of 8192 hands the batch to the pipeline, and
+ *                        the snapshot's next 32 batches stay there.  Read when a snapshot is made too: with no packed group to be
+ *                        part 0 of a snapshot in two parts (bit 7), the largest group in this form may be -- whole, and unfiltered
+ *                        unless the value is 2; a snapshot made under 0 is searched as before whatever the option says later
  *   "fast"               1 | 0   the device-sized path (one host round trip per batch; default 1)
  *   "binned"             1 | 0   groups drop their records into bins of a few queries, scored a bin per workgroup (default 1)
  *   "rec32"              1 | 0   4-byte records in the bins where the doc ids leave room (default 1)
