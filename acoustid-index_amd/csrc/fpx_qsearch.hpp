@@ -21,7 +21,8 @@
 // kernels, k_bw_pattern in profiles/r07_kernel_stats.csv, suggest that the chip serves 72 - 76 G accesses per second whatever they carry:
 // a hypothesis -- counted, profiles/r10_tcp_accesses.txt, the per-lane walk made 3.4 accesses per hash at 0.85 of that rate, this one 2.5.)
 // The hash's own lane takes the head from its group's lane 0 and the `ext` offset from lane 7, does the head's arithmetic
-// and the per-hash statistics once; start, words count, inline limit and the second-word mask go back to the group, and every lane
+// and the per-hash statistics once; what the group needs of it goes back ready-made -- two words indexed by the LINE's word number: which
+// words are the hash's, which of them second words of doubles; and, before the loads, the line's number in the group --, and every lane
 // classifies its own four words of each line where they landed: every inline word is walked, only lists and words in `ext` are tasks.
 // The filtered form keeps the per-lane walk (a word's column is bookkeeping of its own).
 //
@@ -647,22 +648,28 @@ __device__ __forceinline__ void qs_body(const QSearchArgs& a, const GroupArgs& g
     //      access of the vector-memory front end per line where the per-lane walk made three (head, pieces, offset), and no second trip
     //      that depends on the first.  All 64 lines of the wave's round are under way at once, 32 registers per lane.
     //      Then: (1) every lane gets the head (lane 0's first three words) and the `ext` offset (lane 7's last) of ITS OWN hash's line and
-    //      does the head's arithmetic and the per-hash statistics once, as the per-lane walk did; (2) start, words count, inline limit
-    //      and the second-word mask go back to the group, line by line, and every lane classifies its own four words of each line: word
-    //      w = 4 sub + t sits at position p = w - 3 and belongs to the hash iff start <= p < min(start + nwords, inl); (3) ONE
+    //      does the head's arithmetic and the per-hash statistics once, as the per-lane walk did; (2) the hash's words as a mask over
+    //      the line's 32 words, and the second words among them, go back to the group, four lines at a time, and every lane takes its
+    //      nibble of each: word w = 4 sub + t sits at position p = w - 3 and belongs to the hash iff start <= p < min(start + nwords, inl)
+    //      -- worked out once, by the hash's lane, not by each of the eight for each line --; (3) ONE
     //      reservation per wave for the round's records and tasks, the records stored from the lane's 32 registers.  Every inline word
     //      is walked where it landed: only lists and words in `ext` are tasks.
     auto round_coop = [&](uint32_t h, bool valid) {
         const uint32_t sub = lane & 7u;
         uint32_t L[32];
         {
-            const uint32_t gv = (uint32_t)(__ballot((int)valid) >> (lane & 56u)) & 0xFFu;          // the group's valid bits
+            // what is per HASH is made once, by its lane: the number of its line in the group -- 0 for a hash that is no probe: the
+            // group's first line, one address, no HBM, no load under a branch --; a load is then that number from lane k, a shift and
+            // an add to the lane's own base (the byte offset reaches 2^37: only the line's number travels in 32 bits)
+            const uint32_t li = valid ? (h >> HVL) - g->line0 : 0u;
+            const uint8_t* const lb = reinterpret_cast<const uint8_t*>(g->lines) + 16u * sub;
+            uint32_t lk[8];
+            qs_for8([&](auto kc) { constexpr uint32_t k = decltype(kc)::value; lk[k] = qs_group_bcast<k>(li); });
+            // (the eight broadcasts are under way together, one wait for the crossbar: the registers they land in are the lines' own)
+            asm volatile("" : "+v"(lk[0]), "+v"(lk[1]), "+v"(lk[2]), "+v"(lk[3]), "+v"(lk[4]), "+v"(lk[5]), "+v"(lk[6]), "+v"(lk[7]));
             qs_for8([&](auto kc) {
                 constexpr uint32_t k = decltype(kc)::value;
-                const uint32_t hk = qs_group_bcast<k>(h);
-                // (a group whose hash is no probe reads the group's first line: one address, no HBM -- no load under a branch)
-                const uint32_t* lp = ((gv >> k) & 1u) != 0u ? line_of(hk) : g->lines;
-                const uint4 v = gload_u4(reinterpret_cast<const uint8_t*>(lp + 4u * sub));
+                const uint4 v = gload_u4(lb + ((uint64_t)lk[k] * (GROUP_LINE_WORDS * 4u)));
                 L[4 * k] = v.x; L[4 * k + 1] = v.y; L[4 * k + 2] = v.z; L[4 * k + 3] = v.w;
             });
         }
@@ -721,21 +728,28 @@ __device__ __forceinline__ void qs_body(const QSearchArgs& a, const GroupArgs& g
         const uint32_t in_ext = nwords - in_line;
         if (in_ext != 0u) my_reads += 2u;
         const uint32_t chunk = ((h >> GROUP_CHUNK_LOG2) - g->chunk0) & 63u;
-        // (2) every line of the group in turn: start | nwords << 7 | inl << 13 (start <= 96, nwords <= 32, inl <= 29) and the second words
-        uint32_t pa = start | (nwords << 7) | (inl << 13);
+        // (2) the hash's words as the LINE sees them, made once by its lane: bit w of wr = word w of the line (position w - 3) belongs to
+        // the hash -- words start + 3 .. start + in_line + 2, at most word 31: inl <= 29 --, bit w of ws = it is the second word of a
+        // double (a hash without an inline word: in_line = 0, nothing, whatever the shift; ws is not cut to wr: it is only ever looked at
+        // under `keep`, which is).  Both go to the group, line by line, and a lane's share of line k is nibble `sub` of each, put at
+        // nibble k of its own masks.
+        const uint32_t wb = (start + 3u) & 31u;
+        uint32_t wr = ((1u << in_line) - 1u) << wb;
+        uint32_t ws = second << wb;
         uint32_t rm32 = 0, sec32 = 0;                    // the lane's words (register 4 k + t) that belong to their line's hash; second words among them
-        const int p0 = (int)(4u * sub) - 3;              // the position of the lane's first word
-        qs_for8([&](auto kc) {
+        const uint32_t nb = 4u * sub;
+        // (four lines at a time -- eight broadcasts, one wait --: sixteen broadcasts at once cost sixteen registers)
+        auto four_lines = [&](auto kc) {
             constexpr uint32_t k = decltype(kc)::value;
-            const uint32_t ak = qs_group_bcast<k>(pa), bk = qs_group_bcast<k>(second);
-            const int st = (int)(ak & 127u), en = (int)min((ak & 127u) + ((ak >> 7) & 63u), (ak >> 13) & 31u);
-            const int tl = min(max(st - p0, 0), 4), th = min(max(en - p0, 0), 4);
-            const uint32_t rm = ((1u << th) - 1u) & ~((1u << tl) - 1u);
-            const int d = p0 - st;                                            // (<= 28; below -31 the lane has no word of the hash: rm = 0)
-            const uint32_t s4 = (d >= 0 ? bk >> (d & 31) : bk << ((-d) & 31)) & rm;
-            rm32 |= rm << (4u * k); sec32 |= s4 << (4u * k);
-            asm volatile("" : "+v"(pa), "+v"(second), "+v"(rm32), "+v"(sec32));      // (a line after the other: sixteen broadcasts at once cost sixteen registers)
-        });
+            const uint32_t r0 = qs_group_bcast<k>(wr), r1 = qs_group_bcast<k + 1u>(wr), r2 = qs_group_bcast<k + 2u>(wr), r3 = qs_group_bcast<k + 3u>(wr);
+            const uint32_t s0 = qs_group_bcast<k>(ws), s1 = qs_group_bcast<k + 1u>(ws), s2 = qs_group_bcast<k + 2u>(ws), s3 = qs_group_bcast<k + 3u>(ws);
+            auto nib = [&](uint32_t v) -> uint32_t { return __builtin_amdgcn_ubfe(v, nb, 4u); };
+            rm32 |= (nib(r0) << (4u * k)) | (nib(r1) << (4u * k + 4u)) | (nib(r2) << (4u * k + 8u)) | (nib(r3) << (4u * k + 12u));
+            sec32 |= (nib(s0) << (4u * k)) | (nib(s1) << (4u * k + 4u)) | (nib(s2) << (4u * k + 8u)) | (nib(s3) << (4u * k + 12u));
+            asm volatile("" : "+v"(wr), "+v"(ws), "+v"(rm32), "+v"(sec32));
+        };
+        four_lines(qs_idx<0u>{});
+        four_lines(qs_idx<4u>{});
         uint32_t neg32 = 0;                                                   // a gap position and a list reference have bit 31
 #pragma unroll
         for (uint32_t j = 32; j-- != 0u;) neg32 = __builtin_amdgcn_alignbit(neg32, L[j], 31);
