@@ -381,6 +381,7 @@ enum CtxOpt : int {
     OPT_SIDE_WG,
     OPT_HOT_WG,
     OPT_WORDS_WG,
+    OPT_LOW_WG,
     OPT_COUNT
 };
 constexpr int64_t OPT_UNSET = -2;

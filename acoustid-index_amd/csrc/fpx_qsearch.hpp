@@ -32,6 +32,9 @@
 // Option hot_wg = 1 (unfiltered only): such a query is named in the batch's redo list instead, with nothing counted for it, and
 // k_search_classes -- the same body, `CLS` -- walks it once per DOC CLASS, keeping one class of records each time: a doc's postings are
 // all in one class, so each pass counts exactly and the passes' candidates are disjoint.  The batch stays here and nothing backs off.
+// Option low_wg = 1 (unfiltered only): a batch with queries whose floor is 1 or 2 is taken too, by k_search_low -- the same body, `LOW`:
+// such a query's records are sorted in LDS and its scores read off the runs, only the top max_results leave.  A launch of k_search_low
+// carries no redo list: hot_wg is ignored for such a batch.
 // FILT (option query_wg = 2): the same for a group with superseded docs and/or columns outside the snapshot (a live index between a
 // merge and its regroup) -- every word knows its column, as in k_probe_pgroup's per-column walk: a column outside `active` gives no
 // record and no statistic, a doc of a column with a dead set is dropped after it was counted (CTR_DOCS counts before supersession).
@@ -210,10 +213,17 @@ constexpr uint32_t QS_LIST_AHEAD = 8;             // (CLS) loads of 64 docs of a
 // passes <= 64) looks at -- and qs_cell takes the doc's own bits, not its hash's --, so a class fills the filter and the table evenly
 __device__ __forceinline__ uint32_t qs_class(uint32_t rec) { return mix32(rec) >> 27; }
 static_assert(QS_MAX_CLASSES == 32u, "qs_class gives five bits");
-template <int NS, bool QS, bool MEM, bool FILT, bool CLS>
+// ... and a third: k_search_low (LOW true, below; option low_wg = 1) -- the same walk for a batch that has queries with a floor of 1 or 2
+// (the legacy protocol's min_score 1, HTTP queries of 40 hashes or fewer).  For those the filter and the table are no use -- every doc
+// counted is at or above the floor --: their tail SORTS the record array in place and reads the scores off the runs (under
+// `if constexpr (LOW)`, behind the statistics); a query of the same batch with a floor above 2 takes the tail below as it is.
+constexpr uint32_t QS_LOW_CHUNK = 8;              // (LOW) records a lane sorts in registers (two 16-byte pieces): the network's strides below it cost no barrier
+template <int NS, bool QS, bool MEM, bool FILT, bool CLS, bool LOW = false>
 __device__ __forceinline__ void qs_body(const QSearchArgs& a, const GroupArgs& ga)
 {
     static_assert(!(CLS && FILT), "doc classes: the unfiltered walk only");
+    static_assert(!LOW || (!FILT && !CLS && QS_WG == 256u && QS_REC_CAP >= 512u && (QS_REC_CAP & (QS_REC_CAP - 1u)) == 0u),
+                  "low floors: the unfiltered walk only; the sorted tail's scans are written for 256 lanes and a power-of-two array");
 #ifdef FPX_QS_PROF
     unsigned long long t_prev = clock64(), t_sub = 0;
 #endif
@@ -1103,7 +1113,166 @@ __device__ __forceinline__ void qs_body(const QSearchArgs& a, const GroupArgs& g
     const uint32_t floor_q = (uint32_t)__builtin_amdgcn_readfirstlane((int)floor_v);
     const uint32_t sb = kt->a.sb;
     const uint64_t smax = sb >= 32u ? 0xFFFFFFFFull : ((1ull << sb) - 1ull);
-    if (s_over_recs == 0u && !q_redo && nrec != 0u && nrec >= floor_q) {
+    const bool low_q = LOW && floor_q <= 2u;                 // (uniform: the query's own floor chooses its tail)
+    if constexpr (LOW) {
+      // ---- a floor of 1 or 2: every counted doc is a candidate for the table, so there is no table.  (1) the records become absolute
+      //      ids (+ gmin modulo 2^32: a memory segment's doc below gmin was a large value; compareResults' tie-break, src/common.zig:169-171,
+      //      is on the real id); (2) they are SORTED ascending in place, a bitonic network over P = the next power of two, the places
+      //      [nrec, P) padded with 0xFFFFFFFF -- a legal id, but pads are the maximum: the first nrec places hold exactly the records --;
+      //      (3) a doc's score is the length of its run, M the longest; (4) the floor is raised to E = max(floor, rel_floor(M, pct)) --
+      //      finish's relative cut on what this call sees: a part's best is a lower bound of the whole snapshot's, as k_score's
+      //      count-only round argues --; (5) of the docs at or above E only what finish can return leaves: with more than K = max_results
+      //      of them, those above the K-th's score T and, of the docs AT T, the first K - N(> T) in array order, which is id order.
+      //      k_finish gets a superset of what it keeps, in the usual keys.  The filter's area is scratch: a histogram of min(score, 255),
+      //      the waves' totals, M, T and the quota.
+      if (low_q && s_over_recs == 0u && !q_redo && nrec != 0u && nrec >= floor_q && kt->a.opts[(size_t)q * 4u] != 0u) {
+        const uint32_t kmax = kt->a.opts[(size_t)q * 4u], pct = kt->a.opts[(size_t)q * 4u + 2u];
+        const uint32_t gmin_c = kt->ga.g.gmin;
+        uint32_t* const lhist = filter;                      // [256]: docs by min(score, 255)
+        uint32_t* const lsc = filter + 256u;                 // [0..3] a scan's wave totals, [4] M, [5] T, [6] the quota at T
+        uint32_t P = 512u;
+        while (P < nrec) P <<= 1;                            // (<= QS_REC_CAP)
+        __syncthreads();                                     // (the filter's atomics and everybody's reads of the records are done)
+        for (uint32_t i = tid; i < P; i += QS_WG) recs[i] = i < nrec ? recs[i] + gmin_c : 0xFFFFFFFFu;
+        lhist[tid] = 0u;
+        if (tid < 8u) lsc[tid] = 0u;
+        __syncthreads();
+        // (2) the network.  A lane keeps QS_LOW_CHUNK consecutive places in registers for the strides below that -- no barrier between
+        // them --; the strides from QS_LOW_CHUNK up are four compare-exchanges per lane and turn on 16-byte pieces, a barrier each
+        auto cx = [](uint32_t& x, uint32_t& y, bool up) {
+            const uint32_t lo = min(x, y), hi = max(x, y);
+            x = up ? lo : hi; y = up ? hi : lo;
+        };
+        auto chunk_sort = [&](uint32_t k) {                  // k == 0: the merge steps 2, 4 and 8 whole; else step k's strides 4, 2, 1
+            for (uint32_t c = tid; c < P / QS_LOW_CHUNK; c += QS_WG) {
+                uint4* const at = reinterpret_cast<uint4*>(recs + c * QS_LOW_CHUNK);
+                const uint4 x0 = at[0], x1 = at[1];
+                uint32_t v[8] = {x0.x, x0.y, x0.z, x0.w, x1.x, x1.y, x1.z, x1.w};
+                if (k == 0u) {
+#pragma unroll
+                    for (uint32_t kk = 2u; kk <= 8u; kk <<= 1)
+#pragma unroll
+                        for (uint32_t j = kk >> 1; j != 0u; j >>= 1)
+#pragma unroll
+                            for (uint32_t i = 0; i < 8u; ++i)
+                                if ((i & j) == 0u) cx(v[i], v[i | j], kk == 8u ? (c & 1u) == 0u : (i & kk) == 0u);
+                } else {
+                    const bool up = ((c * QS_LOW_CHUNK) & k) == 0u;
+#pragma unroll
+                    for (uint32_t j = 4u; j != 0u; j >>= 1)
+#pragma unroll
+                        for (uint32_t i = 0; i < 8u; ++i)
+                            if ((i & j) == 0u) cx(v[i], v[i | j], up);
+                }
+                at[0] = make_uint4(v[0], v[1], v[2], v[3]); at[1] = make_uint4(v[4], v[5], v[6], v[7]);
+            }
+        };
+        static_assert(QS_LOW_CHUNK == 8u, "chunk_sort is written for eight places");
+        chunk_sort(0u);
+        __syncthreads();
+        for (uint32_t k = 2u * QS_LOW_CHUNK; k <= P; k <<= 1) {
+            for (uint32_t j = k >> 1; j >= QS_LOW_CHUNK; j >>= 1) {
+                for (uint32_t w = tid; w < P / 8u; w += QS_WG) {
+                    const uint32_t t0 = 4u * w, i = ((t0 & ~(j - 1u)) << 1) | (t0 & (j - 1u));       // (four pairs side by side: j >= 8)
+                    uint4* const pa = reinterpret_cast<uint4*>(recs + i);
+                    uint4* const pb = reinterpret_cast<uint4*>(recs + i + j);
+                    uint4 x = *pa, y = *pb;
+                    const bool up = (i & k) == 0u;
+                    cx(x.x, y.x, up); cx(x.y, y.y, up); cx(x.z, y.z, up); cx(x.w, y.w, up);
+                    *pa = x; *pb = y;
+                }
+                __syncthreads();
+            }
+            chunk_sort(k);
+            __syncthreads();
+        }
+        // (3) runs.  A lane takes C consecutive places -- C odd: the lanes' places fall into different banks --; a run belongs to the
+        // lane that holds its head, its length is one, or found by bisection (the array is sorted: a run ends where the doc does)
+        const uint32_t C = ((nrec + QS_WG - 1u) / QS_WG) | 1u;
+        const uint32_t i0 = min(tid * C, nrec), i1 = min(i0 + C, nrec);
+        auto run_len = [&](uint32_t i, uint32_t doc) -> uint32_t {
+            if (i + 1u >= nrec || recs[i + 1u] != doc) return 1u;
+            uint32_t lo = i + 2u, hi = nrec;
+            while (lo < hi) {
+                const uint32_t mid = (lo + hi) >> 1;
+                if (recs[mid] == doc) lo = mid + 1u; else hi = mid;
+            }
+            return lo - i;
+        };
+        auto for_runs = [&](auto&& f) {                      // f(doc, score) for every run whose head is among the lane's places
+            uint32_t prev = (i0 != 0u && i0 < nrec) ? recs[i0 - 1u] : 0u;
+            for (uint32_t i = i0; i < i1; ++i) {
+                const uint32_t doc = recs[i];
+                if (i == 0u || doc != prev) f(doc, run_len(i, doc));
+                prev = doc;
+            }
+        };
+        auto wave_incl = [&](uint32_t v) -> uint32_t {       // (the whole wave is here)
+            const uint32_t incl = scan16(v);
+            const uint32_t r0 = (uint32_t)__builtin_amdgcn_readlane((int)incl, 15), r1 = (uint32_t)__builtin_amdgcn_readlane((int)incl, 31),
+                           r2 = (uint32_t)__builtin_amdgcn_readlane((int)incl, 47);
+            const uint32_t row = lane >> 4;
+            return incl + (row >= 1u ? r0 : 0u) + (row >= 2u ? r1 : 0u) + (row >= 3u ? r2 : 0u);
+        };
+        {
+            uint32_t ones = 0u, best = 0u;
+            for_runs([&](uint32_t, uint32_t len) {
+                best = max(best, len);
+                if (len == 1u) ++ones; else atomicAdd(&lhist[min(len, 255u)], 1u);
+            });
+            if (ones != 0u) atomicAdd(&lhist[1], ones);
+            if (best != 0u) atomicMax(&lsc[4], best);
+        }
+        __syncthreads();
+        // (4)
+        const uint32_t best_q = lsc[4];
+        const uint32_t cut = max(floor_q, rel_floor(best_q, pct));
+        if (best_q >= cut) {                                 // (uniform)
+            // (5) lane t: S(t) = docs at or above the cut whose slot is >= t.  T is the slot where S reaches K; slot 255 holds every
+            // score from 255 up, so there nothing is cut (a superset: at most 8192 / 255 docs).  With K or fewer docs nobody writes: T = 0
+            const uint32_t cb = min(cut, 255u);
+            const uint32_t hm = tid >= cb ? lhist[tid] : 0u;
+            const uint32_t wi = wave_incl(hm);
+            if (lane == 63u) lsc[tid >> 6] = wi;
+            __syncthreads();
+            const uint32_t t0 = lsc[0], t1 = lsc[1], t2 = lsc[2], t3 = lsc[3], wv = tid >> 6;
+            const uint32_t incl = wi + (wv >= 1u ? t0 : 0u) + (wv >= 2u ? t1 : 0u) + (wv >= 3u ? t2 : 0u);
+            const uint32_t above = t0 + t1 + t2 + t3 - incl;                       // S(t + 1)
+            if (above + hm >= kmax && above < kmax) {
+                lsc[5] = tid == 255u ? 254u : tid;
+                lsc[6] = tid == 255u ? 0u : kmax - above;
+            }
+            __syncthreads();
+            const uint32_t tcut = lsc[5], quota = lsc[6];
+            uint32_t rank = 0u;                              // docs AT tcut in the places before the lane's
+            if (quota != 0u) {                               // (uniform)
+                uint32_t mine = 0u;
+                for_runs([&](uint32_t, uint32_t len) { mine += len == tcut ? 1u : 0u; });
+                const uint32_t mi = wave_incl(mine);
+                if (lane == 63u) lsc[tid >> 6] = mi;         // (the totals above were read before the last barrier)
+                __syncthreads();
+                rank = mi - mine + (wv >= 1u ? lsc[0] : 0u) + (wv >= 2u ? lsc[1] : 0u) + (wv >= 3u ? lsc[2] : 0u);
+            }
+            // the existing hand-over: the query's buffer in LDS (its first SB_CAND), the rest to the shared list
+            for_runs([&](uint32_t doc, uint32_t count) {
+                if (count < cut || count < tcut) return;
+                if (count == tcut && rank++ >= quota) return;
+                if ((uint64_t)count > smax) atomicMax(&kt->a.counters[CTR_MAXSCORE], (unsigned long long)count);
+                const uint64_t sc = (uint64_t)count > smax ? smax : (uint64_t)count;
+                const uint64_t qpart = sb >= 32u ? 0ull : ((uint64_t)q << (32u + sb));
+                const uint64_t key = qpart | ((smax - sc) << 32) | doc;
+                const uint32_t at = atomicAdd(&s_ccnt, 1u);
+                if (at < SB_CAND) cbuf[at] = key;
+                else {
+                    const unsigned long long gi = atomicAdd(&kt->a.counters[CTR_CANDS], 1ull);
+                    if (gi < kt->a.cand_cap) kt->a.cands[gi] = key;
+                    s_cshared = 1u;
+                }
+            });
+        }
+      }
+    }
+    if (!low_q && s_over_recs == 0u && !q_redo && nrec != 0u && nrec >= floor_q) {
         uint32_t passes = 1u;
         for (uint32_t pass = 0; pass < passes; ++pass) {
             if (pass != 0u) {
@@ -1230,6 +1399,16 @@ template <int NS, bool MEM>
 __global__ __launch_bounds__(QS_WG) FPX_QS_OCC void k_search_classes(QSearchArgs a, GroupArgs ga)
 {
     qs_body<NS, true, MEM, false, true>(a, ga);
+}
+
+// k_search_low (option low_wg = 1): k_search_query's unfiltered body for a batch that HAS queries with a floor of 1 or 2 -- those take the
+// sorted tail (qs_body: `LOW`), the batch's other queries the usual one.  Launched for such a batch only: every other batch is
+// k_search_query's, whatever the option says.  No redo list (a.redo is null: option hot_wg is ignored for such a batch -- a query whose
+// records outgrow the array hands the batch to the pipeline, with the back-off) and no doc classes.  The same two by-value parameters.
+template <int NS, bool QS, bool MEM>
+__global__ __launch_bounds__(QS_WG) FPX_QS_OCC void k_search_low(QSearchArgs a, GroupArgs ga)
+{
+    qs_body<NS, QS, MEM, false, false, true>(a, ga);
 }
 
 // zeroes what a batch of k_search_query adds to: the batch's counters and the statistics sets (one launch instead of two memsets)

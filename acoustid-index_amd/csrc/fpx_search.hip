@@ -11,7 +11,8 @@
 //   A. a snapshot that is ONE packed group (the resident index between merges): k_search_query (fpx_qsearch.hpp), a QUERY PER WORKGROUP --
 //      dedup, the group's lines, counting and the floor in one kernel, the hit records never leaving the CU -- then k_finish, k_publish
 //      (run_query_wg; run_side_wg for the file segments next to the group; run_words_wg -- option words_wg, k_search_words in
-//      fpx_qwords.hpp -- for a snapshot that is one group in directory + words form).
+//      fpx_qwords.hpp -- for a snapshot that is one group in directory + words form).  A batch with queries whose floor is 1 or 2 is B's,
+//      or -- option low_wg, an unfiltered packed group -- run_query_wg's with k_search_low in k_search_query's place.
 //   B. everything else, the pipeline over all the batch's hashes (make_keys, launch_probes; run_device_sized, run_single or run_general):
 //      1. k_make_keys*     (hash, q) keys, packed hash << QB | q; ordered by hash bucket (fpx_keyorder.hpp / fpx_sort.hip) or per query in LDS:
 //                          duplicates become adjacent (dedupSorted) and neighbouring probes walk neighbouring lines
@@ -676,12 +677,19 @@ static int ensure_def_lists(Batch& b, bool side_wg)
 
 // ---- the query-per-workgroup paths: who takes them --------------------------------------------------------------------------------
 // the queries' rule: short enough for the kernels' hash set, and a floor above the legacy protocol's
-static bool queries_fit_wg(const uint64_t* offsets, const fpx_opts* opts, uint32_t B)
+// (low_ok: floors of 1 and 2 are allowed -- option low_wg, k_search_low's sorted tail --; *has_low: the batch has such a query)
+static bool queries_fit_wg(const uint64_t* offsets, const fpx_opts* opts, uint32_t B, bool low_ok = false, bool* has_low = nullptr)
 {
+    bool low = false;
     for (uint32_t q = 0; q < B; ++q) {
         const uint64_t raw_len = offsets[q + 1] - offsets[q];
-        if (raw_len > QS_MAX_HASHES || query_floor(opts[q], raw_len) <= 2u) return false;
+        if (raw_len > QS_MAX_HASHES) return false;
+        if (query_floor(opts[q], raw_len) <= 2u) {
+            if (!low_ok) return false;
+            low = true;
+        }
     }
+    if (has_low) *has_low = low;
     return true;
 }
 // a group for k_search_query's filtered instantiation: superseded docs, or columns outside the snapshot
@@ -690,13 +698,14 @@ static bool group_filtered(const GroupDesc& gd) { return gd.any_dead != 0u || gd
 // ONE WORKGROUP PER QUERY (fpx_qsearch.hpp): the snapshot is one packed group and nothing else, every column of it searched, no superseded
 // docs -- the resident index between merges --, the queries short enough for their hash set and their floor above the legacy protocol's.
 // Option query_wg 2: a group with superseded docs or columns outside the snapshot too, by the kernel's filtered instantiation (*filt).
-static bool takes_query_wg(const Snapshot* snap, const uint64_t* offsets, const fpx_opts* opts, uint32_t B, bool* filt)
+// Option low_wg 1: queries with a floor of 1 or 2 too, where the group is NOT filtered (*low: the batch has such a query -- k_search_low).
+static bool takes_query_wg(const Snapshot* snap, const uint64_t* offsets, const fpx_opts* opts, uint32_t B, bool* filt, bool* low)
 {
     const int64_t query_wg = ctx_opt(snap->ctx, OPT_QUERY_WG);
     if (!(snap->n_file == 0 && snap->n_solo == 0 && snap->n_group == 1 && snap->n_direct != 0 &&
           (snap->n_mem == 0 || snap->mem_items == 0 || snap->d_memtab != nullptr) && snap->groups[0]->packed && query_wg != 0)) return false;
     *filt = group_filtered(snap->h_group[0]);
-    return (!*filt || query_wg == 2) && queries_fit_wg(offsets, opts, B);
+    return (!*filt || query_wg == 2) && queries_fit_wg(offsets, opts, B, !*filt && ctx_opt(snap->ctx, OPT_LOW_WG) == 1, low);
 }
 // ... and the same for the file segments NEXT TO the group (fpx_qside.hpp; option side_wg = 1): a snapshot -- part 1 of a live one, or a
 // whole young index -- of small decoded and direct-addressed-alone segments only, none of them a hash-window slice, no group, no
@@ -742,6 +751,16 @@ static void launch_search_classes(bool ns8, bool mem, dim3 grid, hipStream_t st,
     if (ns8) { if (mem) FPX_LC(8, true); else FPX_LC(8, false); }
     else { if (mem) FPX_LC(16, true); else FPX_LC(16, false); }
 #undef FPX_LC
+}
+// ... and k_search_low's (a batch with queries whose floor is 1 or 2, option low_wg; unfiltered)
+static void launch_search_low(bool ns8, bool qs, bool mem, dim3 grid, hipStream_t st, const QSearchArgs& qa, const GroupArgs& g)
+{
+#define FPX_LL(NS, QSV, MEM) hipLaunchKernelGGL((k_search_low<NS, QSV, MEM>), grid, dim3(QS_WG), QS_LDS_BYTES, st, qa, g)
+#define FPX_LL_MEM(NS, QSV) do { if (mem) FPX_LL(NS, QSV, true); else FPX_LL(NS, QSV, false); } while (0)
+    if (ns8) { if (qs) FPX_LL_MEM(8, true); else FPX_LL_MEM(8, false); }
+    else { if (qs) FPX_LL_MEM(16, true); else FPX_LL_MEM(16, false); }
+#undef FPX_LL_MEM
+#undef FPX_LL
 }
 // the end of a query-per-workgroup path: results, the kernel's statistics sets, per-query statistics, the next batch's hints
 static int finish_wg_path(Batch& b, const ResultsTo& to, uint64_t Cf, uint32_t path_bits)
@@ -789,14 +808,26 @@ static int redo_hot_queries(Batch& b, QSearchArgs qa, const GroupArgs& gargs, bo
 
 // Dedup, probe, count and floor happen in ONE kernel, no keys are made or ordered, no record reaches HBM.  A batch that kernel hands back
 // (hot hashes: a query's records outgrow its LDS array) returns FPX_REDO_QS: run_with_redos gives it to the pipeline.
-static int run_query_wg(Batch& b, bool filt)
+// low: the batch has queries with a floor of 1 or 2 (option low_wg let it in; never with filt) -- k_search_low, which has no redo list.
+// Every other batch is k_search_query's exactly as before, whatever that option says.
+static int run_query_wg(Batch& b, bool filt, bool low)
 {
     Snapshot* snap = b.snap; Workspace* ws = b.ws; hipStream_t st = b.st; const uint32_t B = b.B; int rc;
     const bool ns8 = snap->groups[0]->ns == 8u;
     // (option hot_wg = 1, unfiltered: the batch's redo list -- B entries, behind the slots and their counts)
-    const bool hot_wg = !filt && ctx_opt(snap->ctx, OPT_HOT_WG) == 1;
+    const bool hot_wg = !filt && !low && ctx_opt(snap->ctx, OPT_HOT_WG) == 1;
     CandSlots cs;
     if ((rc = ensure_cand_slots(ws, B, hot_wg ? (size_t)B : 0, &cs))) return rc;
+    if (low) {
+        // (a query with a low floor hands over up to max_results candidates -- the legacy protocol's 500 --, all of them through the shared
+        // list once they are more than its slots: the list is sized for that, not for the first guess of 64 per query)
+        size_t want = 0;
+        for (uint32_t q = 0; q < B; ++q) {
+            const bool low_q = query_floor(b.opts[q], b.offsets[q + 1] - b.offsets[q]) <= 2u;
+            want += low_q ? std::min<size_t>(b.opts[q].max_results, QS_REC_CAP) + 32u : 64u;
+        }
+        if (ws->cap_cands < want && (rc = grow_pair(ws->d_cands, &ws->cap_cands, want))) return rc;
+    }
     const uint32_t sbf = 32u - b.qb;
     hipLaunchKernelGGL(k_qs_zero, dim3(8), dim3(256), 0, st, ws->d_counters, ws->d_def_count, (uint32_t)b.def_words);
     FPX_HIP(hipEventRecord(ws->ev_probe0, st));
@@ -825,7 +856,9 @@ static int run_query_wg(Batch& b, bool filt)
         qa.next_q = (FPX_QS_DYN && alone) ? ws->d_def_count + c : nullptr;
         qa.stagger = alone ? QS_STAGGER : 0u;
         if (up_chunks) FPX_HIP(hipStreamWaitEvent(st, ws->ev_chunk[c], 0));           // (the piece's hashes have arrived; the next piece is on its way)
-        launch_search_query(ns8, b.want_q, qa.mem_tab != nullptr, filt, dim3(std::min<uint32_t>(qa.q_end - qa.q_begin, (uint32_t)cus * QS_WGS_PER_CU)), st, qa, gargs);
+        const dim3 grid(std::min<uint32_t>(qa.q_end - qa.q_begin, (uint32_t)cus * QS_WGS_PER_CU));
+        if (low) launch_search_low(ns8, b.want_q, qa.mem_tab != nullptr, grid, st, qa, gargs);
+        else launch_search_query(ns8, b.want_q, qa.mem_tab != nullptr, filt, grid, st, qa, gargs);
         if (up_chunks && c + 1u < up_chunks && (rc = upload_piece(b, c + 1u))) return rc;       // (the next piece crosses PCIe under this kernel)
     }
     FPX_HIP(hipGetLastError());
@@ -855,7 +888,7 @@ static int run_query_wg(Batch& b, bool filt)
         Cf = ws->h_counters[CTR_CANDS];
         if ((rc = finish_crowded(b, sbf, cs, to, Cf))) return rc;
     }
-    return finish_wg_path(b, to, Cf, 4u | 64u | (filt ? 256u : 0u) | (R != 0 ? 1024u : 0u));
+    return finish_wg_path(b, to, Cf, 4u | 64u | (filt ? 256u : 0u) | (R != 0 ? 1024u : 0u) | (low ? 4096u : 0u));
 }
 
 // ... and the file segments next to the group, by k_search_side
@@ -1646,9 +1679,9 @@ static int run_batch(Snapshot* snap, Workspace* ws, const QueryBatch* resident, 
     //      group or none: never both) or, under option words_wg, k_search_words; B: the pipeline -- for one query its single-launch form, else device-sized (below) or general
     const bool single_fast = B == 1 && !partial && !ex && !no_fast && P != 0 && out_cap <= SINGLE_OUT_MAX &&
                              (snap->n_lean == 0 || P * snap->n_file < lean_min_probes(snap->ctx));
-    bool query_wg = false, words_wg = false, side_wg = false, filt = false;
+    bool query_wg = false, words_wg = false, side_wg = false, filt = false, low = false;
     if (!ex && !no_fast && !no_qs && !single_fast && B >= 2u && P != 0 && b.qb <= 24u) {
-        query_wg = takes_query_wg(snap, offsets, opts, B, &filt);
+        query_wg = takes_query_wg(snap, offsets, opts, B, &filt, &low);
         words_wg = !query_wg && takes_words_wg(snap, offsets, opts, B, &filt);
         side_wg = !query_wg && !words_wg && takes_side_wg(snap, offsets, opts, B);
         if (query_wg || words_wg || side_wg) {
@@ -1668,7 +1701,7 @@ static int run_batch(Snapshot* snap, Workspace* ws, const QueryBatch* resident, 
     // per-query scan statistics, when the caller asked for them (a single query's are the call's totals: search_split)
     b.want_q = (q_blocks || q_docs) && B >= 2u && !score_only;
     if (b.want_q && (rc = grow(&ws->d_qstats, &ws->cap_qstats, (size_t)B + 1))) return rc;
-    if (query_wg) return run_query_wg(b, filt);
+    if (query_wg) return run_query_wg(b, filt, low);
     if (words_wg) return run_words_wg(b, filt);
     if (side_wg) return run_side_wg(b);
 
@@ -1693,9 +1726,11 @@ static bool parts_take(const Snapshot* snap, const uint64_t* offsets, const fpx_
     // (a part 0 in directory + words form -- made under words_wg -- while THAT option allows it)
     const int64_t query_wg = ctx_opt(snap->ctx, snap->part[0]->groups[0]->packed ? OPT_QUERY_WG : OPT_WORDS_WG);
     if (query_wg == 0) return false;
-    if (query_wg != 2 && group_filtered(snap->part[0]->h_group[0])) return false;
+    const bool filtered = group_filtered(snap->part[0]->h_group[0]), packed = snap->part[0]->groups[0]->packed;
+    if (query_wg != 2 && filtered) return false;
     if (bits_for(B) > 24u || offsets[B] == offsets[0]) return false;
-    return queries_fit_wg(offsets, opts, B);
+    // (floors of 1 and 2: takes_query_wg's rule -- option low_wg, a packed, unfiltered part 0)
+    return queries_fit_wg(offsets, opts, B, packed && !filtered && ctx_opt(snap->ctx, OPT_LOW_WG) == 1);
 }
 
 // one batch on one workspace, redone where a path hands it back; FPX_OK, FPX_SPLIT (the caller halves the batch) or an error
