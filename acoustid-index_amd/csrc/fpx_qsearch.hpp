@@ -2,6 +2,8 @@
 // dedupSorted (:489-499), FileSegment.search for all sixteen segments (src/FileSegment.zig:135-180), SearchResults.incr and the
 // min_score filter of finish (src/common.zig:121-145) in one kernel, the query's hit records never leaving the CU.
 // Part of the fpx_search.hip translation unit (after fpx_pgroup.hpp and fpx_score_bin.hpp, whose line layout and candidate hand-over it shares).
+// fpx_qframe.hpp, behind this file, holds the same LDS layout, counting tail and hand-over ONCE for k_search_side and k_search_words (sizes
+// asserted equal to the ones here); this kernel keeps its own text of them -- qs_cold_args(), the next query's loads, CLS and LOW run through it.
 //
 // Rounds 2-5 ran the batch as a pipeline over ALL its query hashes: keys made and ordered by hash bucket (two kernels + a radix pass),
 // one probe kernel that drops the hit records -- 7 per query hash on the 100 M index, 237 MB per batch of 8192 -- into bins in HBM, one

@@ -47,6 +47,7 @@
 #include "fpx_score.hpp"
 #include "fpx_score_bin.hpp"
 #include "fpx_qsearch.hpp"
+#include "fpx_qframe.hpp"
 #include "fpx_qside.hpp"
 #include "fpx_qwords.hpp"
 
@@ -762,6 +763,36 @@ static void launch_search_low(bool ns8, bool qs, bool mem, dim3 grid, hipStream_
 #undef FPX_LL_MEM
 #undef FPX_LL
 }
+// a query-per-workgroup path opens: the queries' candidate slots (`extra_words` of the caller's behind them), the counters and statistics
+// sets zeroed, the probe's first event -- and the arguments every such kernel takes, from the batch (Args: QFrameArgs | QSearchArgs,
+// by their same-named members; which queries a launch takes is the caller's to say)
+template <class Args>
+static int open_wg_path(Batch& b, size_t extra_words, CandSlots* cs, Args* a)
+{
+    Workspace* ws = b.ws; int rc;
+    if ((rc = ensure_cand_slots(ws, b.B, extra_words, cs))) return rc;
+    hipLaunchKernelGGL(k_qs_zero, dim3(8), dim3(256), 0, b.st, ws->d_counters, ws->d_def_count, (uint32_t)b.def_words);
+    FPX_HIP(hipEventRecord(ws->ev_probe0, b.st));
+    a->hashes_base = b.d_hashes_base; a->offsets = b.d_offsets; a->opts = b.d_opts; a->sb = 32u - b.qb;
+    a->cands = ws->d_cands[0]; a->cand_cap = ws->cap_cands; a->qcand = cs->qcand; a->qcand_n = cs->qcand_n;
+    a->counters = ws->d_counters; a->stat_sets = device_stat_sets(b);
+    a->qstats = b.want_q ? ws->d_qstats : nullptr; a->cancel = b.cancel;
+    return FPX_OK;
+}
+// ... and its first pass closes behind the kernel's launches: k_finish over the queries' own slots, the batch's counters and statistics sets
+// into the host's mapped copies, the wait.  FPX_REDO_QS: the kernel handed the batch back (run_with_redos: the pipeline)
+static int close_wg_pass(Batch& b, uint32_t sb, const CandSlots& cs, ResultsTo* to)
+{
+    Workspace* ws = b.ws; int rc;
+    FPX_HIP(hipGetLastError());
+    FPX_HIP(hipEventRecord(ws->ev_probe1, b.st));
+    if ((rc = results_target(b, to))) return rc;
+    launch_finish(b, ws->d_cands[0], 0, sb, cs, to->res, to->n, b.stats != nullptr);
+    if ((rc = publish(b, true))) return rc;
+    FPX_HIP(hipEventRecord(ws->ev_end, b.st));
+    FPX_SYNC_BATCH(b);
+    return handed_back(ws, b.snap) ? FPX_REDO_QS : FPX_OK;
+}
 // the end of a query-per-workgroup path: results, the kernel's statistics sets, per-query statistics, the next batch's hints
 static int finish_wg_path(Batch& b, const ResultsTo& to, uint64_t Cf, uint32_t path_bits)
 {
@@ -816,8 +847,6 @@ static int run_query_wg(Batch& b, bool filt, bool low)
     const bool ns8 = snap->groups[0]->ns == 8u;
     // (option hot_wg = 1, unfiltered: the batch's redo list -- B entries, behind the slots and their counts)
     const bool hot_wg = !filt && !low && ctx_opt(snap->ctx, OPT_HOT_WG) == 1;
-    CandSlots cs;
-    if ((rc = ensure_cand_slots(ws, B, hot_wg ? (size_t)B : 0, &cs))) return rc;
     if (low) {
         // (a query with a low floor hands over up to max_results candidates -- the legacy protocol's 500 --, all of them through the shared
         // list once they are more than its slots: the list is sized for that, not for the first guess of 64 per query)
@@ -828,20 +857,16 @@ static int run_query_wg(Batch& b, bool filt, bool low)
         }
         if (ws->cap_cands < want && (rc = grow_pair(ws->d_cands, &ws->cap_cands, want))) return rc;
     }
-    const uint32_t sbf = 32u - b.qb;
-    hipLaunchKernelGGL(k_qs_zero, dim3(8), dim3(256), 0, st, ws->d_counters, ws->d_def_count, (uint32_t)b.def_words);
-    FPX_HIP(hipEventRecord(ws->ev_probe0, st));
+    CandSlots cs;
+    QSearchArgs qa{};
+    if ((rc = open_wg_path(b, hot_wg ? (size_t)B : 0, &cs, &qa))) return rc;
     struct Running {                                 // batches of this context inside their k_search_query launches, this one included
         std::atomic<int>* c; int before;
         explicit Running(std::atomic<int>* c_) : c(c_), before(c_->fetch_add(1)) {}
         ~Running() { c->fetch_sub(1); }
     } running(&snap->ctx->qs_running);
     const bool alone = running.before == 0;
-    QSearchArgs qa{};
-    qa.hashes_base = b.d_hashes_base; qa.offsets = b.d_offsets; qa.opts = b.d_opts; qa.q_begin = 0u; qa.q_end = B; qa.sb = sbf;
-    qa.cands = ws->d_cands[0]; qa.cand_cap = ws->cap_cands; qa.qcand = cs.qcand; qa.qcand_n = cs.qcand_n;
-    qa.counters = ws->d_counters; qa.stat_sets = device_stat_sets(b);
-    qa.qstats = b.want_q ? ws->d_qstats : nullptr; qa.cancel = b.cancel;
+    qa.q_begin = 0u; qa.q_end = B;
     if (snap->n_mem != 0 && snap->mem_items != 0) { qa.mem_tab = snap->d_memtab; qa.mem_bucket = snap->d_membucket; qa.mem_bits = snap->d_membits; }
     if (hot_wg) { qa.redo = reinterpret_cast<unsigned long long*>(cs.extra); qa.redo_cap = B; }
     const GroupArgs gargs{snap->h_group[0], snap->d_direct};
@@ -861,15 +886,9 @@ static int run_query_wg(Batch& b, bool filt, bool low)
         else launch_search_query(ns8, b.want_q, qa.mem_tab != nullptr, filt, grid, st, qa, gargs);
         if (up_chunks && c + 1u < up_chunks && (rc = upload_piece(b, c + 1u))) return rc;       // (the next piece crosses PCIe under this kernel)
     }
-    FPX_HIP(hipGetLastError());
-    FPX_HIP(hipEventRecord(ws->ev_probe1, st));
+    // (the batch's counters and statistics sets go to the host's mapped copies here, after the first pass, and again after a redo)
     ResultsTo to;
-    if ((rc = results_target(b, &to))) return rc;
-    launch_finish(b, ws->d_cands[0], 0, sbf, cs, to.res, to.n, b.stats != nullptr);
-    // (the batch's counters and statistics sets into the host's mapped copies: after the first pass, and again after a redo)
-    if ((rc = publish(b, true))) return rc;
-    FPX_HIP(hipEventRecord(ws->ev_end, st));
-    FPX_SYNC_BATCH(b);
+    if ((rc = close_wg_pass(b, qa.sb, cs, &to)) != FPX_OK && rc != FPX_REDO_QS) return rc;
 #ifdef FPX_QS_PROF
     fprintf(stderr, "qs_prof clocks/query: setup %.0f dedup %.0f rounds %.0f tasks %.0f count+exact %.0f handover %.0f", ws->h_counters[CTR_HIST] / (double)B, ws->h_counters[CTR_HIST + 1] / (double)B,
             ws->h_counters[CTR_HIST + 2] / (double)B, ws->h_counters[CTR_HIST + 3] / (double)B, ws->h_counters[CTR_HIST + 4] / (double)B, ws->h_counters[CTR_HIST + 5] / (double)B);
@@ -878,7 +897,7 @@ static int run_query_wg(Batch& b, bool filt, bool low)
             ws->h_counters[CTR_HIST + 7] / (double)B, ws->h_counters[CTR_HIST + 8] / (double)B, ws->h_counters[CTR_HIST + 9] / (double)B, ws->h_counters[CTR_HIST + 10] / (double)B,
             ws->h_counters[CTR_HIST + 11] / (double)B);
 #endif
-    if (handed_back(ws, snap)) return FPX_REDO_QS;
+    if (rc) return rc;                                         // (handed back)
     // (the shared list's length is known to the host only behind a synchronisation of its own: the sort below needs it)
     const uint64_t R = hot_wg ? ws->h_counters[CTR_REDO] : 0;
     if (R != 0 && (rc = redo_hot_queries(b, qa, gargs, ns8, cus, R))) return rc;
@@ -886,7 +905,7 @@ static int run_query_wg(Batch& b, bool filt, bool low)
     uint64_t Cf = 0;
     if (ws->h_counters[CTR_CANDS] != 0 || R != 0) {
         Cf = ws->h_counters[CTR_CANDS];
-        if ((rc = finish_crowded(b, sbf, cs, to, Cf))) return rc;
+        if ((rc = finish_crowded(b, qa.sb, cs, to, Cf))) return rc;
     }
     return finish_wg_path(b, to, Cf, 4u | 64u | (filt ? 256u : 0u) | (R != 0 ? 1024u : 0u) | (low ? 4096u : 0u));
 }
@@ -894,39 +913,26 @@ static int run_query_wg(Batch& b, bool filt, bool low)
 // ... and the file segments next to the group, by k_search_side
 static int run_side_wg(Batch& b)
 {
-    Snapshot* snap = b.snap; Workspace* ws = b.ws; hipStream_t st = b.st; const uint32_t B = b.B; int rc;
+    Snapshot* snap = b.snap; const uint32_t B = b.B; int rc;
     CandSlots cs;
-    if ((rc = ensure_cand_slots(ws, B, 0, &cs))) return rc;
-    const uint32_t sbf = 32u - b.qb;
-    hipLaunchKernelGGL(k_qs_zero, dim3(8), dim3(256), 0, st, ws->d_counters, ws->d_def_count, (uint32_t)b.def_words);
-    FPX_HIP(hipEventRecord(ws->ev_probe0, st));
     SideArgs sa{};
-    sa.hashes_base = b.d_hashes_base; sa.offsets = b.d_offsets; sa.opts = b.d_opts; sa.B = B; sa.sb = sbf;
-    sa.cands = ws->d_cands[0]; sa.cand_cap = ws->cap_cands; sa.qcand = cs.qcand; sa.qcand_n = cs.qcand_n;
-    sa.counters = ws->d_counters; sa.stat_sets = device_stat_sets(b);
-    sa.qstats = b.want_q ? ws->d_qstats : nullptr; sa.cancel = b.cancel;
+    if ((rc = open_wg_path(b, 0, &cs, &sa.f))) return rc;
+    sa.f.B = B;
     sa.small = snap->d_small; sa.n_small = snap->n_small; sa.solo = snap->d_solo; sa.n_solo = snap->n_solo;
-    // as many workgroups as the chip holds at once (LDS: SIDE_WGS_PER_CU per CU); each takes every gridDim.x-th query
+    // as many workgroups as the chip holds at once (LDS: QF_WGS_PER_CU per CU); each takes every gridDim.x-th query
     const int cus = device_cus(snap->ctx);
-    hipLaunchKernelGGL(k_search_side, dim3(std::min<uint32_t>(B, (uint32_t)cus * SIDE_WGS_PER_CU)), dim3(SIDE_WG), SIDE_LDS_BYTES, st, sa);
-    FPX_HIP(hipGetLastError());
-    FPX_HIP(hipEventRecord(ws->ev_probe1, st));
+    hipLaunchKernelGGL(k_search_side, dim3(std::min<uint32_t>(B, (uint32_t)cus * QF_WGS_PER_CU)), dim3(QF_WG), QF_LDS_BYTES, b.st, sa);
     ResultsTo to;
-    if ((rc = results_target(b, &to))) return rc;
-    launch_finish(b, ws->d_cands[0], 0, sbf, cs, to.res, to.n, b.stats != nullptr);
-    if ((rc = publish(b, true))) return rc;
-    FPX_HIP(hipEventRecord(ws->ev_end, st));
-    FPX_SYNC_BATCH(b);
-    if (handed_back(ws, snap)) return FPX_REDO_QS;           // (that snapshot or part alone: run_with_redos)
-    const uint64_t Cf = ws->h_counters[CTR_CANDS];
-    if (Cf != 0 && (rc = finish_crowded(b, sbf, cs, to, Cf))) return rc;
+    if ((rc = close_wg_pass(b, sa.f.sb, cs, &to))) return rc;           // (handed back: that snapshot or part alone goes to the pipeline)
+    const uint64_t Cf = b.ws->h_counters[CTR_CANDS];
+    if (Cf != 0 && (rc = finish_crowded(b, sa.f.sb, cs, to, Cf))) return rc;
     return finish_wg_path(b, to, Cf, 512u);
 }
 
 // k_search_words' instantiations: columns of a directory line (8 | 16), the memory segments' table, filtered
 static void launch_search_words(bool ns8, bool mem, bool filt, dim3 grid, hipStream_t st, const WordsArgs& wa, const GroupArgs& g)
 {
-#define FPX_LW(NS, MEM, FILT) hipLaunchKernelGGL((k_search_words<NS, MEM, FILT>), grid, dim3(WORDS_WG), WORDS_LDS_BYTES, st, wa, g)
+#define FPX_LW(NS, MEM, FILT) hipLaunchKernelGGL((k_search_words<NS, MEM, FILT>), grid, dim3(QF_WG), QF_LDS_BYTES, st, wa, g)
 #define FPX_LW_MEM(NS, FILT) do { if (mem) FPX_LW(NS, true, FILT); else FPX_LW(NS, false, FILT); } while (0)
 #define FPX_LW_NS(FILT) do { if (ns8) FPX_LW_MEM(8, FILT); else FPX_LW_MEM(16, FILT); } while (0)
     if (filt) FPX_LW_NS(true); else FPX_LW_NS(false);
@@ -937,33 +943,20 @@ static void launch_search_words(bool ns8, bool mem, bool filt, dim3 grid, hipStr
 // ... and a group in directory + words form, by k_search_words (the memory segments behind their table with it)
 static int run_words_wg(Batch& b, bool filt)
 {
-    Snapshot* snap = b.snap; Workspace* ws = b.ws; hipStream_t st = b.st; const uint32_t B = b.B; int rc;
+    Snapshot* snap = b.snap; const uint32_t B = b.B; int rc;
     CandSlots cs;
-    if ((rc = ensure_cand_slots(ws, B, 0, &cs))) return rc;
-    const uint32_t sbf = 32u - b.qb;
-    hipLaunchKernelGGL(k_qs_zero, dim3(8), dim3(256), 0, st, ws->d_counters, ws->d_def_count, (uint32_t)b.def_words);
-    FPX_HIP(hipEventRecord(ws->ev_probe0, st));
     WordsArgs wa{};
-    wa.hashes_base = b.d_hashes_base; wa.offsets = b.d_offsets; wa.opts = b.d_opts; wa.B = B; wa.sb = sbf;
-    wa.cands = ws->d_cands[0]; wa.cand_cap = ws->cap_cands; wa.qcand = cs.qcand; wa.qcand_n = cs.qcand_n;
-    wa.counters = ws->d_counters; wa.stat_sets = device_stat_sets(b);
-    wa.qstats = b.want_q ? ws->d_qstats : nullptr; wa.cancel = b.cancel;
+    if ((rc = open_wg_path(b, 0, &cs, &wa.f))) return rc;
+    wa.f.B = B;
     if (snap->n_mem != 0 && snap->mem_items != 0) { wa.mem_tab = snap->d_memtab; wa.mem_bucket = snap->d_membucket; wa.mem_bits = snap->d_membits; }
     const GroupArgs gargs{snap->h_group[0], snap->d_direct};
-    // as many workgroups as the chip holds at once (LDS: WORDS_WGS_PER_CU per CU); each takes every gridDim.x-th query
+    // as many workgroups as the chip holds at once (LDS: QF_WGS_PER_CU per CU); each takes every gridDim.x-th query
     const int cus = device_cus(snap->ctx);
-    launch_search_words(snap->groups[0]->ns == 8u, wa.mem_tab != nullptr, filt, dim3(std::min<uint32_t>(B, (uint32_t)cus * WORDS_WGS_PER_CU)), st, wa, gargs);
-    FPX_HIP(hipGetLastError());
-    FPX_HIP(hipEventRecord(ws->ev_probe1, st));
+    launch_search_words(snap->groups[0]->ns == 8u, wa.mem_tab != nullptr, filt, dim3(std::min<uint32_t>(B, (uint32_t)cus * QF_WGS_PER_CU)), b.st, wa, gargs);
     ResultsTo to;
-    if ((rc = results_target(b, &to))) return rc;
-    launch_finish(b, ws->d_cands[0], 0, sbf, cs, to.res, to.n, b.stats != nullptr);
-    if ((rc = publish(b, true))) return rc;
-    FPX_HIP(hipEventRecord(ws->ev_end, st));
-    FPX_SYNC_BATCH(b);
-    if (handed_back(ws, snap)) return FPX_REDO_QS;           // (run_with_redos: the pipeline)
-    const uint64_t Cf = ws->h_counters[CTR_CANDS];
-    if (Cf != 0 && (rc = finish_crowded(b, sbf, cs, to, Cf))) return rc;
+    if ((rc = close_wg_pass(b, wa.f.sb, cs, &to))) return rc;           // (handed back: the pipeline)
+    const uint64_t Cf = b.ws->h_counters[CTR_CANDS];
+    if (Cf != 0 && (rc = finish_crowded(b, wa.f.sb, cs, to, Cf))) return rc;
     return finish_wg_path(b, to, Cf, 4u | 2048u | (filt ? 256u : 0u));
 }
 
