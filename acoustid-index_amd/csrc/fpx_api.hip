@@ -424,7 +424,7 @@ static const OptInfo OPT_TABLE[OPT_COUNT] = {
     /* OPT_SIDE_WG */            {"side_wg", "FPX_SIDE_WG", 0, 0, false},                        // 0 | 1: the file segments next to the group (small decoded, direct-addressed alone) by the pipeline | a query per workgroup (fpx_qside.hpp)
     /* OPT_HOT_WG */             {"hot_wg", "FPX_HOT_WG", 0, 0, false},                          // 0 | 1: a query whose records outgrow k_search_query's LDS array hands the batch to the pipeline | is redone in doc classes by k_search_classes (fpx_qsearch.hpp; unfiltered only)
     /* OPT_WORDS_WG */           {"words_wg", "FPX_WORDS_WG", 0, 0, false},                      // 0 | 1 | 2: a snapshot that is ONE group in directory + words form by the pipeline | a query per workgroup (fpx_qwords.hpp) | as 1, a group with superseded docs or masked columns too
-    /* OPT_LOW_WG */             {"low_wg", "FPX_LOW_WG", 0, 0, false},                          // 0 | 1: a batch with queries whose floor is 1 or 2 (the legacy protocol, short fingerprints) goes to the pipeline | stays with k_search_query's path, by k_search_low (fpx_qsearch.hpp; one packed, unfiltered group)
+    /* OPT_LOW_WG */             {"low_wg", "FPX_LOW_WG", 0, 0, false},                          // 0 | 1 | 2: a batch with queries whose floor is 1 or 2 (the legacy protocol, short fingerprints) goes to the pipeline | stays with k_search_query's path, by k_search_low (fpx_qsearch.hpp; one packed, unfiltered group) | as 1, a group with superseded docs or masked columns too (k_search_low_filt; such a group is on that path under query_wg 2 only)
 };
 
 int64_t ctx_opt(const Ctx* c, CtxOpt o)

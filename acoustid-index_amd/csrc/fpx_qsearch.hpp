@@ -36,7 +36,8 @@
 // all in one class, so each pass counts exactly and the passes' candidates are disjoint.  The batch stays here and nothing backs off.
 // Option low_wg = 1 (unfiltered only): a batch with queries whose floor is 1 or 2 is taken too, by k_search_low -- the same body, `LOW`:
 // such a query's records are sorted in LDS and its scores read off the runs, only the top max_results leave.  A launch of k_search_low
-// carries no redo list: hot_wg is ignored for such a batch.
+// carries no redo list: hot_wg is ignored for such a batch.  Option low_wg = 2: as 1, and under query_wg = 2 a FILTERED group too, by
+// k_search_low_filt -- the filtered walk below leaves live docs only in the record array, which is all the sorted tail asks for.
 // FILT (option query_wg = 2): the same for a group with superseded docs and/or columns outside the snapshot (a live index between a
 // merge and its regroup) -- every word knows its column, as in k_probe_pgroup's per-column walk: a column outside `active` gives no
 // record and no statistic, a doc of a column with a dead set is dropped after it was counted (CTR_DOCS counts before supersession).
@@ -216,6 +217,7 @@ constexpr uint32_t QS_LIST_AHEAD = 8;             // (CLS) loads of 64 docs of a
 __device__ __forceinline__ uint32_t qs_class(uint32_t rec) { return mix32(rec) >> 27; }
 static_assert(QS_MAX_CLASSES == 32u, "qs_class gives five bits");
 // ... and a third: k_search_low (LOW true, below; option low_wg = 1) -- the same walk for a batch that has queries with a floor of 1 or 2
+// -- and a fourth, the same with FILT: k_search_low_filt (option low_wg = 2) --
 // (the legacy protocol's min_score 1, HTTP queries of 40 hashes or fewer).  For those the filter and the table are no use -- every doc
 // counted is at or above the floor --: their tail SORTS the record array in place and reads the scores off the runs (under
 // `if constexpr (LOW)`, behind the statistics); a query of the same batch with a floor above 2 takes the tail below as it is.
@@ -224,8 +226,8 @@ template <int NS, bool QS, bool MEM, bool FILT, bool CLS, bool LOW = false>
 __device__ __forceinline__ void qs_body(const QSearchArgs& a, const GroupArgs& ga)
 {
     static_assert(!(CLS && FILT), "doc classes: the unfiltered walk only");
-    static_assert(!LOW || (!FILT && !CLS && QS_WG == 256u && QS_REC_CAP >= 512u && (QS_REC_CAP & (QS_REC_CAP - 1u)) == 0u),
-                  "low floors: the unfiltered walk only; the sorted tail's scans are written for 256 lanes and a power-of-two array");
+    static_assert(!LOW || (!CLS && QS_WG == 256u && QS_REC_CAP >= 512u && (QS_REC_CAP & (QS_REC_CAP - 1u)) == 0u),
+                  "low floors: no doc classes; the sorted tail's scans are written for 256 lanes and a power-of-two array");
 #ifdef FPX_QS_PROF
     unsigned long long t_prev = clock64(), t_sub = 0;
 #endif
@@ -1411,6 +1413,20 @@ template <int NS, bool QS, bool MEM>
 __global__ __launch_bounds__(QS_WG) FPX_QS_OCC void k_search_low(QSearchArgs a, GroupArgs ga)
 {
     qs_body<NS, QS, MEM, false, false, true>(a, ga);
+}
+
+// k_search_low_filt (option low_wg = 2 under query_wg = 2): the same for a group with superseded docs and/or columns outside the snapshot
+// -- k_search_query's FILTERED body with the sorted tail.  The filtered walk drops a superseded doc where it would be emitted (the lane's
+// own words, the tasks' words and list heads, the wave-walked lists), a column outside the snapshot gives no record, the memory segments'
+// table holds live postings only: when s_count is final the record array holds live docs only, as doc - gmin -- what the tail takes as it
+// is.  Its scratch is the filter's area, which the task queue left before (tcols, behind the queue, was last read by the last task).
+// Blocks, docs, qstats and the histograms are the filtered form's (counted before supersession); no redo list; a query over QS_REC_CAP
+// records or over the filtered queue's QS_TASKS_FILT tasks hands the batch to the pipeline.  A kernel of its own name: k_search_low keeps
+// its three parameters.
+template <int NS, bool QS, bool MEM>
+__global__ __launch_bounds__(QS_WG) FPX_QS_OCC void k_search_low_filt(QSearchArgs a, GroupArgs ga)
+{
+    qs_body<NS, QS, MEM, true, false, true>(a, ga);
 }
 
 // zeroes what a batch of k_search_query adds to: the batch's counters and the statistics sets (one launch instead of two memsets)

@@ -12,7 +12,8 @@
 //      dedup, the group's lines, counting and the floor in one kernel, the hit records never leaving the CU -- then k_finish, k_publish
 //      (run_query_wg; run_side_wg for the file segments next to the group; run_words_wg -- option words_wg, k_search_words in
 //      fpx_qwords.hpp -- for a snapshot that is one group in directory + words form).  A batch with queries whose floor is 1 or 2 is B's,
-//      or -- option low_wg, an unfiltered packed group -- run_query_wg's with k_search_low in k_search_query's place.
+//      or -- option low_wg: 1 an unfiltered packed group, 2 a filtered one too -- run_query_wg's with k_search_low (k_search_low_filt) in
+//      k_search_query's place.
 //   B. everything else, the pipeline over all the batch's hashes (make_keys, launch_probes; run_device_sized, run_single or run_general):
 //      1. k_make_keys*     (hash, q) keys, packed hash << QB | q; ordered by hash bucket (fpx_keyorder.hpp / fpx_sort.hip) or per query in LDS:
 //                          duplicates become adjacent (dedupSorted) and neighbouring probes walk neighbouring lines
@@ -699,14 +700,20 @@ static bool group_filtered(const GroupDesc& gd) { return gd.any_dead != 0u || gd
 // ONE WORKGROUP PER QUERY (fpx_qsearch.hpp): the snapshot is one packed group and nothing else, every column of it searched, no superseded
 // docs -- the resident index between merges --, the queries short enough for their hash set and their floor above the legacy protocol's.
 // Option query_wg 2: a group with superseded docs or columns outside the snapshot too, by the kernel's filtered instantiation (*filt).
-// Option low_wg 1: queries with a floor of 1 or 2 too, where the group is NOT filtered (*low: the batch has such a query -- k_search_low).
+// Option low_wg 1: queries with a floor of 1 or 2 too, where the group is NOT filtered (*low: the batch has such a query -- k_search_low);
+// 2: where it is filtered too (k_search_low_filt; a filtered group is only ever here under query_wg 2).
+static bool low_floors_ok(const Ctx* ctx, bool filtered)
+{
+    const int64_t low_wg = ctx_opt(ctx, OPT_LOW_WG);
+    return low_wg == 2 || (low_wg == 1 && !filtered);
+}
 static bool takes_query_wg(const Snapshot* snap, const uint64_t* offsets, const fpx_opts* opts, uint32_t B, bool* filt, bool* low)
 {
     const int64_t query_wg = ctx_opt(snap->ctx, OPT_QUERY_WG);
     if (!(snap->n_file == 0 && snap->n_solo == 0 && snap->n_group == 1 && snap->n_direct != 0 &&
           (snap->n_mem == 0 || snap->mem_items == 0 || snap->d_memtab != nullptr) && snap->groups[0]->packed && query_wg != 0)) return false;
     *filt = group_filtered(snap->h_group[0]);
-    return (!*filt || query_wg == 2) && queries_fit_wg(offsets, opts, B, !*filt && ctx_opt(snap->ctx, OPT_LOW_WG) == 1, low);
+    return (!*filt || query_wg == 2) && queries_fit_wg(offsets, opts, B, low_floors_ok(snap->ctx, *filt), low);
 }
 // ... and the same for the file segments NEXT TO the group (fpx_qside.hpp; option side_wg = 1): a snapshot -- part 1 of a live one, or a
 // whole young index -- of small decoded and direct-addressed-alone segments only, none of them a hash-window slice, no group, no
@@ -762,6 +769,16 @@ static void launch_search_low(bool ns8, bool qs, bool mem, dim3 grid, hipStream_
     else { if (qs) FPX_LL_MEM(16, true); else FPX_LL_MEM(16, false); }
 #undef FPX_LL_MEM
 #undef FPX_LL
+}
+// ... and k_search_low_filt's (the same on a filtered group: option low_wg = 2 under query_wg = 2)
+static void launch_search_low_filt(bool ns8, bool qs, bool mem, dim3 grid, hipStream_t st, const QSearchArgs& qa, const GroupArgs& g)
+{
+#define FPX_LF(NS, QSV, MEM) hipLaunchKernelGGL((k_search_low_filt<NS, QSV, MEM>), grid, dim3(QS_WG), QS_LDS_BYTES, st, qa, g)
+#define FPX_LF_MEM(NS, QSV) do { if (mem) FPX_LF(NS, QSV, true); else FPX_LF(NS, QSV, false); } while (0)
+    if (ns8) { if (qs) FPX_LF_MEM(8, true); else FPX_LF_MEM(8, false); }
+    else { if (qs) FPX_LF_MEM(16, true); else FPX_LF_MEM(16, false); }
+#undef FPX_LF_MEM
+#undef FPX_LF
 }
 // a query-per-workgroup path opens: the queries' candidate slots (`extra_words` of the caller's behind them), the counters and statistics
 // sets zeroed, the probe's first event -- and the arguments every such kernel takes, from the batch (Args: QFrameArgs | QSearchArgs,
@@ -839,7 +856,8 @@ static int redo_hot_queries(Batch& b, QSearchArgs qa, const GroupArgs& gargs, bo
 
 // Dedup, probe, count and floor happen in ONE kernel, no keys are made or ordered, no record reaches HBM.  A batch that kernel hands back
 // (hot hashes: a query's records outgrow its LDS array) returns FPX_REDO_QS: run_with_redos gives it to the pipeline.
-// low: the batch has queries with a floor of 1 or 2 (option low_wg let it in; never with filt) -- k_search_low, which has no redo list.
+// low: the batch has queries with a floor of 1 or 2 (option low_wg let it in; with filt under low_wg 2 only) -- k_search_low, or
+// k_search_low_filt on a filtered group; neither has a redo list.
 // Every other batch is k_search_query's exactly as before, whatever that option says.
 static int run_query_wg(Batch& b, bool filt, bool low)
 {
@@ -882,7 +900,8 @@ static int run_query_wg(Batch& b, bool filt, bool low)
         qa.stagger = alone ? QS_STAGGER : 0u;
         if (up_chunks) FPX_HIP(hipStreamWaitEvent(st, ws->ev_chunk[c], 0));           // (the piece's hashes have arrived; the next piece is on its way)
         const dim3 grid(std::min<uint32_t>(qa.q_end - qa.q_begin, (uint32_t)cus * QS_WGS_PER_CU));
-        if (low) launch_search_low(ns8, b.want_q, qa.mem_tab != nullptr, grid, st, qa, gargs);
+        if (low && filt) launch_search_low_filt(ns8, b.want_q, qa.mem_tab != nullptr, grid, st, qa, gargs);
+        else if (low) launch_search_low(ns8, b.want_q, qa.mem_tab != nullptr, grid, st, qa, gargs);
         else launch_search_query(ns8, b.want_q, qa.mem_tab != nullptr, filt, grid, st, qa, gargs);
         if (up_chunks && c + 1u < up_chunks && (rc = upload_piece(b, c + 1u))) return rc;       // (the next piece crosses PCIe under this kernel)
     }
@@ -1722,8 +1741,8 @@ static bool parts_take(const Snapshot* snap, const uint64_t* offsets, const fpx_
     const bool filtered = group_filtered(snap->part[0]->h_group[0]), packed = snap->part[0]->groups[0]->packed;
     if (query_wg != 2 && filtered) return false;
     if (bits_for(B) > 24u || offsets[B] == offsets[0]) return false;
-    // (floors of 1 and 2: takes_query_wg's rule -- option low_wg, a packed, unfiltered part 0)
-    return queries_fit_wg(offsets, opts, B, packed && !filtered && ctx_opt(snap->ctx, OPT_LOW_WG) == 1);
+    // (floors of 1 and 2: takes_query_wg's rule -- option low_wg, a packed part 0; a filtered one under 2 only)
+    return queries_fit_wg(offsets, opts, B, packed && low_floors_ok(snap->ctx, filtered));
 }
 
 // one batch on one workspace, redone where a path hands it back; FPX_OK, FPX_SPLIT (the caller halves the batch) or an error

@@ -61,10 +61,11 @@ class Context:
         that path (Stats.path_flags bit 10).  'words_wg': 0 | 1 | 2 -- a snapshot that is one group in directory + words form (every group
         that is not packed) searched by the pipeline | a query per workgroup (Stats.path_flags bit 11) | as 1, a group with superseded
         docs or masked columns too (bits 11 and 8); read when a snapshot is made as well: part 0 of a snapshot in two parts may then be
-        such a group.  'low_wg': 0 | 1 -- a batch with queries whose score floor is 1 or 2 (the legacy protocol's min_score 1, default
+        such a group.  'low_wg': 0 | 1 | 2 -- a batch with queries whose score floor is 1 or 2 (the legacy protocol's min_score 1, default
         floors of queries of 40 hashes or fewer) is the pipeline's | stays on the query-per-workgroup path of a packed, unfiltered group:
         such queries' records are sorted in LDS and only what finish can return is handed over (Stats.path_flags bit 12, with bits 6
-        and 2; 'hot_wg' is ignored for such a batch)"""
+        and 2; 'hot_wg' is ignored for such a batch) | as 1, and on a group with superseded docs or masked columns too, which only
+        'query_wg' 2 puts on that path (bits 12 and 8)"""
         check(lib().fpx_ctx_set_option(self.h, name.encode(), int(value)))
 
     def trim(self):

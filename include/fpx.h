@@ -94,7 +94,8 @@ typedef struct {
                                    query per workgroup ("words_wg" 1 | 2; bit 2 is set with it, bit 8 when its filtered form ran, bit 6
                                    -- k_search_query's -- is not),
                                    bit 12: the batch (or its part 0) ran k_search_low: it has queries with a score floor of 1 or 2 and
-                                   stayed a query per workgroup ("low_wg" 1; bits 6 and 2 are set with it) */
+                                   stayed a query per workgroup ("low_wg" 1 | 2; bits 6 and 2 are set with it, and bit 8 when the group is
+                                   filtered -- k_search_low_filt, "low_wg" 2 under "query_wg" 2) */
     uint64_t probe_kernel_fetched_bytes; /* block bytes the main probe kernel really fetched, in 128-byte lines: a probe
                                    whose hash the segment's presence bits know to be absent counts as a visited block (as in
                                    the reference) without the block being read, and a block that is read costs two lines up
@@ -148,7 +149,7 @@ int  fpx_ctx_device(const fpx_ctx *ctx);     /* the HIP ordinal the context live
  *                        the snapshot's next 32 batches stay there.  Read when a snapshot is made too: with no packed group to be
  *                        part 0 of a snapshot in two parts (bit 7), the largest group in this form may be -- whole, and unfiltered
  *                        unless the value is 2; a snapshot made under 0 is searched as before whatever the option says later
- *   "low_wg"             0 | 1   a batch with queries whose score floor is 1 or 2 -- the legacy protocol's min_score 1, the default
+ *   "low_wg"             0 | 1 | 2   a batch with queries whose score floor is 1 or 2 -- the legacy protocol's min_score 1, the default
  *                        floor of a query of 40 hashes or fewer -- is the pipeline's, whatever the snapshot (default 0) | stays a QUERY
  *                        PER WORKGROUP where "query_wg" would have taken it but for those floors: ONE packed group, unfiltered (a
  *                        filtered group under "query_wg" 2 keeps the pipeline for such a batch), or such a part 0 of a snapshot in
@@ -156,8 +157,11 @@ int  fpx_ctx_device(const fpx_ctx *ctx);     /* the HIP ordinal the context live
  *                        records in LDS, reads the scores off the runs, raises the floor by the query's best score and hands over
  *                        only the top max_results; the batch's other queries are counted as in k_search_query.  A batch without
  *                        such a query runs k_search_query as before.  "hot_wg" is ignored for a batch that runs k_search_low: a
- *                        query whose records outgrow the array of 8192 hands the batch to the pipeline, with the back-off
- *   "fast"               1 | 0   the device-sized path (one host round trip per batch; default 1)
+ *                        query whose records outgrow the array of 8192 hands the batch to the pipeline, with the back-off | as 1, and
+ *                        so does such a batch on a FILTERED group -- superseded docs and/or columns outside the snapshot, which
+ *                        "query_wg" 2 alone puts on this path; with "query_wg" 1 the value 2 is 1 --, by k_search_low_filt (bits 12
+ *                        and 8): the filtered walk leaves live docs only for the same sorted tail.  On an unfiltered group 2 is 1
+ *   "fast"              1 | 0   the device-sized path (one host round trip per batch; default 1)
  *   "binned"             1 | 0   groups drop their records into bins of a few queries, scored a bin per workgroup (default 1)
  *   "rec32"              1 | 0   4-byte records in the bins where the doc ids leave room (default 1)
  *   "local_sort_max", "order_min_pairs"   pair counts that choose how a batch's keys are ordered
