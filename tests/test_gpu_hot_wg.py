@@ -24,43 +24,27 @@ profiles/r11_hot_wg.txt; "all heavy cases" = every case but the superseded-doc o
 import numpy as np
 import pytest
 
+import wg_harness as wg
+from wg_harness import FILTERED, QS_REC_CAP, QUERY_WG, REDONE, SECOND_TRIP, U64, figures as _figures, growth as _growth, hist as _hist, post as _post
+
 pytestmark = pytest.mark.gpu
 
 HOT, SHARED, CROWD, SINGLE = 0x12345678, 0x0BADF00D, 0x51515151, 0x70000000
-QUERY_WG, SECOND_TRIP, FILTERED, REDONE = 64, 2, 256, 1024
-QS_REC_CAP = 8192
-U64 = np.uint64
+OPTIONS = ("hot_wg", "query_wg")
 
 
 @pytest.fixture(scope="module")
 def env():
-    from fpx_testlib import fpx, oracle, Pair
-    ctx = fpx.Context(0)
-    yield fpx, oracle, Pair, ctx
-    _reset(ctx)
-
-
-def _reset(ctx):
-    for name in ("hot_wg", "query_wg"):
-        ctx.set_option(name, -1)
-    ctx.set_option("group_packed", -2)
+    e = wg.open_context()
+    yield e
+    wg.reset(e[3], OPTIONS)
 
 
 @pytest.fixture
 def hot(env, monkeypatch):
     """every file segment a direct-addressed candidate, groups packed; the options reset afterwards"""
-    fpx, oracle, Pair, ctx = env
-    monkeypatch.setenv("FPX_DIRECT_MIN_ITEMS", "0")
-    _reset(ctx)
-    ctx.set_option("group_packed", 1)
-    try:
-        yield fpx, oracle, Pair, ctx
-    finally:
-        _reset(ctx)
-
-
-def _post(hash_, ids):
-    return (U64(hash_) << U64(32)) | np.asarray(ids, dtype=U64)
+    with wg.settings(env, monkeypatch, OPTIONS, group_packed=1) as e:
+        yield e
 
 
 class World:
@@ -112,15 +96,6 @@ class World:
         return self.p.osnap.search(q, 40, None, 10, with_stats=True)[1].scanned_docs
 
 
-def _hist(ctx):
-    h, unb = ctx.scan_histograms()
-    return h.as_dict(), unb
-
-
-def _growth(a, b):
-    return {k: ([y - x for x, y in zip(a[k], b[k])] if isinstance(a[k], list) else b[k] - a[k]) for k in a}
-
-
 def _drain(p, plain):
     """batches until the snapshot's back-off after a hand-back is over"""
     for _ in range(40):
@@ -130,7 +105,9 @@ def _drain(p, plain):
 
 
 def _both(fpx, ctx, w, queries, opts, plain, redone=True, want=0):
-    """Pair.check under hot_wg = 1 with the path bits asserted, then the batch under hot_wg = 1 and 0, everything equal"""
+    """Pair.check under hot_wg = 1 with the path bits asserted, then the batch under hot_wg = 1 and 0, everything equal.  Not the harness's
+    both(): between the two runs a plain batch shows that nothing backed off, so the histograms are read once more (h1b) before the run
+    under 0, and a handed-back batch's back-off is drained at the end"""
     p = w.p
     p.http = fpx.http_options()
     want1 = QUERY_WG | (REDONE if redone else 0) | want
@@ -156,9 +133,9 @@ def _both(fpx, ctx, w, queries, opts, plain, redone=True, want=0):
     finally:
         ctx.set_option("hot_wg", -1)
     assert g1 == got and g0 == got
-    t1, t0 = (s1.scanned_blocks, s1.scanned_docs, s1.probes, s1.hits), (s0.scanned_blocks, s0.scanned_docs, s0.probes, s0.hits)
+    t1, t0 = _figures(s1)[:wg.FOUR], _figures(s0)[:wg.FOUR]      # (blocks, docs, probes and hits: this suite never compared algorithmic_bytes)
     assert t1 == t0, (t1, t0)
-    assert t1 == (st.scanned_blocks, st.scanned_docs, st.probes, st.hits)
+    assert t1 == _figures(st)[:wg.FOUR]
     assert [int(x) for x in qb1] == [int(x) for x in qb0] and [int(x) for x in qd1] == [int(x) for x in qd0]
     assert _growth(h0, h1) == _growth(h1b, h2), (_growth(h0, h1), _growth(h1b, h2))
     assert unb1 == 0 and unb2 == 0, (unb1, unb2)

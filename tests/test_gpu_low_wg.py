@@ -8,169 +8,47 @@ Every case goes through Pair.check under the option (results and every query's s
 asserted, and is then run again under the option and under low_wg = 0 and compared byte for byte: results, scanned_blocks, scanned_docs,
 probes, hits, algorithmic_bytes, per-query blocks / docs and the growth of the context's scan histograms (nothing unbucketed).  The
 groups are tiny (group_packed = 1, FPX_DIRECT_MIN_ITEMS = 0), one at a time: each case is the smallest shape that reaches its branch."""
+import functools
+
 import numpy as np
 import pytest
 
+import wg_harness as wg
+from wg_harness import (FILTERED, GROUP, LOW, QS_MAX_HASHES, QUERY_WG, SECOND_TRIP, TWO_PARTS, U64, HOT8, HOT1,
+                        aimed as _aimed, figures as _figures, legacy as _legacy, noise as _noise, rand_items as _rand_items, rows as _rows,
+                        sampled as _sampled)
+
 pytestmark = pytest.mark.gpu
 
-SHARED, DOUBLE, HOT8, HOT1, CROWD, SINGLE = 0x2BADF00D, 0x37770000, 0x4BCDEF01, 0x4CCDEF05, 0x51515151, 0x70000000
-LOW, FILTERED, TWO_PARTS, QUERY_WG, GROUP, SECOND_TRIP = 4096, 256, 128, 64, 4, 2
-QS_MAX_HASHES, QS_REC_CAP = 4096, 8192
-U64 = np.uint64
+SHARED, DOUBLE, CROWD, SINGLE = 0x2BADF00D, 0x37770000, 0x51515151, 0x70000000
 OPTIONS = ("low_wg", "hot_wg", "query_wg", "direct_min_items")
+_usual = wg.usual(SHARED, DOUBLE)
 
 
 @pytest.fixture(scope="module")
 def env():
-    from fpx_testlib import fpx, oracle, Pair
-    ctx = fpx.Context(0)
-    yield fpx, oracle, Pair, ctx
-    _reset(ctx)
-
-
-def _reset(ctx):
-    for name in OPTIONS:
-        ctx.set_option(name, -1)
-    ctx.set_option("group_packed", -2)
+    e = wg.open_context()
+    yield e
+    wg.reset(e[3], OPTIONS)
 
 
 @pytest.fixture
 def tiny(env, monkeypatch):
     """every file segment a direct-addressed candidate unless a test says otherwise, groups packed"""
-    fpx, oracle, Pair, ctx = env
-    monkeypatch.setenv("FPX_DIRECT_MIN_ITEMS", "0")
-    _reset(ctx)
-    ctx.set_option("group_packed", 1)
-    try:
-        yield fpx, oracle, Pair, ctx
-    finally:
-        _reset(ctx)
+    with wg.settings(env, monkeypatch, OPTIONS, group_packed=1) as e:
+        yield e
 
 
-def _post(hash_, ids):
-    return (U64(hash_) << U64(32)) | np.asarray(ids, dtype=U64)
-
-
-def _rand_items(rng, ids, nh, extra=()):
-    docs = np.asarray(ids, dtype=U64)
-    h = rng.integers(0, 1 << 32, (len(docs), nh), dtype=U64)
-    return np.unique(np.concatenate([((h << U64(32)) | docs[:, None]).ravel()] + [_post(hh, d) for hh, d in extra]))
-
-
-def _rows(items, doc):
-    return (items[(items & U64(0xFFFFFFFF)) == U64(doc)] >> U64(32)).astype(np.uint32)
-
-
-def _noise(rng, n):
-    return rng.integers(0, 1 << 32, n, dtype=U64).astype(np.uint32)
-
-
-class World:
+def World(Pair, ctx):
     """a Pair whose file segments meet in ONE packed group; checkpoints, a merged segment and memory segments next to it"""
-
-    def __init__(self, Pair, ctx):
-        self.p, self.ctx, self.items, self.commit = Pair(ctx), ctx, [], 1
-
-    def file(self, items, ids, form="column"):
-        self.ctx.set_option("direct_min_items", (1 << 20) if form == "blocks" else 0)
-        ids = np.asarray(ids, dtype=np.uint32)
-        self.p.add_file(items, int(ids.min()), int(ids.max()), self.commit, ids)
-        self.items.append(items)
-        self.commit += 1
-
-    def columns(self, rng, cols, per, nh, extra=lambda s, ids: [], first=1):
-        for s in range(cols):
-            ids = np.arange(first + s * per, first + (s + 1) * per, dtype=np.int64)
-            self.file(_rand_items(rng, ids, nh, extra(s, ids)), ids)
-        self.p.finish()
-        assert all(g.grouped for g in self.p.gpu_segs[:cols]), [g.layout_reason for g in self.p.gpu_segs]
-        info = self.p.gpu_segs[0].group_info()
-        assert info["packed"] == 1 and info["columns"] == cols and info["line_columns"] == (8 if cols <= 8 else 16), info
-        return self.p, first + cols * per
-
-    def memory(self, items, ids):
-        ids = np.asarray(ids, dtype=np.uint32)
-        self.p.add_memory(items, int(ids.min()), int(ids.max()), self.commit, ids)
-        self.items.append(items)
-        self.commit += 1
-
-    def finish(self):
-        self.ctx.set_option("direct_min_items", -1)
-        self.p.finish()
-        return self.p
-
-
-def _aimed(rng, items, qlen, extra=()):
-    """a query of `qlen` hashes: a random doc's of `items` (half the query at most), `extra`, the rest noise"""
-    doc = items[rng.integers(0, len(items))] & U64(0xFFFFFFFF)
-    parts = [_rows(items, doc)[:max(1, qlen // 2)], np.asarray(extra, dtype=np.uint32)]
-    have = sum(len(x) for x in parts)
-    if qlen > have:
-        parts.append(_noise(rng, qlen - have))
-    q = np.concatenate(parts)
-    rng.shuffle(q)
-    return q
-
-
-def _sampled(rng, items, n):
-    """the hashes of `n` postings drawn from `items`: about n docs with a score of 1, a few with 2"""
-    return (items[rng.choice(len(items), n, replace=False)] >> U64(32)).astype(np.uint32)
-
-
-def _hist(ctx):
-    h, unb = ctx.scan_histograms()
-    return h.as_dict(), unb
-
-
-def _growth(a, b):
-    return {k: ([y - x for x, y in zip(a[k], b[k])] if isinstance(a[k], list) else b[k] - a[k]) for k in a}
-
-
-def _figures(s):
-    return (s.scanned_blocks, s.scanned_docs, s.probes, s.hits, s.algorithmic_bytes)
+    return wg.World(Pair, ctx, packed=1)
 
 
 def _both(ctx, p, queries, opts, want=LOW | QUERY_WG | GROUP, want_not=0, also=()):
-    """Pair.check under low_wg = 1 with the path bits asserted, then the batch under the option and under 0, everything equal"""
-    try:
-        for name, value in also:
-            ctx.set_option(name, value)
-        ctx.set_option("low_wg", 1)
-        got, st = p.check(queries, opts)
-        print(f"low_wg 1: path_flags {st.path_flags}, blocks / docs / probes / hits / bytes {_figures(st)}")
-        assert st.path_flags & want == want and not st.path_flags & want_not, (st.path_flags, want, want_not)
-        h0, _ = _hist(ctx)
-        g1, s1, qb1, qd1 = p.reader.search_batch_stats(queries, opts)
-        h1, unb1 = _hist(ctx)
-        ctx.set_option("low_wg", 0)
-        g0, s0, qb0, qd0 = p.reader.search_batch_stats(queries, opts)
-        h2, unb2 = _hist(ctx)
-    finally:
-        ctx.set_option("low_wg", -1)
-        for name, _ in also:
-            ctx.set_option(name, -1)
-    print(f"low_wg 0: path_flags {s0.path_flags}, {_figures(s0)}; low_wg 1 again: {s1.path_flags}, {_figures(s1)}")
-    assert not s0.path_flags & LOW, s0.path_flags
-    if want & LOW:
-        assert not s0.path_flags & QUERY_WG, s0.path_flags         # (a batch with a low floor: the pipeline's, as before)
-    assert s1.path_flags & want == want and not s1.path_flags & want_not, (s1.path_flags, want, want_not)
-    assert g1 == got and g0 == got
-    assert _figures(s1) == _figures(s0), (_figures(s1), _figures(s0))
-    assert _figures(s1) == _figures(st), (_figures(s1), _figures(st))
-    assert [int(x) for x in qb1] == [int(x) for x in qb0] and [int(x) for x in qd1] == [int(x) for x in qd0]
-    assert _growth(h0, h1) == _growth(h1, h2), (_growth(h0, h1), _growth(h1, h2))
-    assert unb1 == 0 and unb2 == 0, (unb1, unb2)
-    return got, st
-
-
-def _legacy(fpx):
-    """the legacy protocol's search (src/legacy.zig:192-197)"""
-    return fpx.SearchOptions(max_results=500, min_score=1, min_score_pct=10)
-
-
-def _usual(s, ids):
-    """SHARED a list of 2 / 3 / 4 / 70 docs, DOUBLE a double in every column"""
-    return [(SHARED, ids[: [2, 3, 4, 70][s % 4]]), (DOUBLE, ids[:2])]
+    """Pair.check under low_wg = 1 with the path bits asserted, then the batch under the option and under 0, everything equal.  Under 0 a
+    batch with a low floor is the pipeline's, as before: bit 6 clear as well"""
+    return wg.both(ctx, p, queries, opts, "low_wg", 1, clear=LOW | (QUERY_WG if want & LOW else 0), want=want, want_not=want_not, also=also,
+                   compare=wg.WITH_BYTES)      # (algorithmic_bytes too)
 
 
 # ---- 1. the legacy protocol -----------------------------------------------------------------------------------------------------
@@ -351,19 +229,7 @@ def _records(p, q):
     return p.osnap.search(q, 40, 1, 0, with_stats=True)[1].scanned_docs
 
 
-def _exact(p, rng, head, singles, target):
-    """a query of exactly `target` records: `head`, then hashes of one doc each (one of them may be some other doc's too), fifty of noise"""
-    noise = _noise(rng, 50)
-    n = target - 1000 * 8 * (HOT8 in head) - 1000 * (HOT1 in head)
-    for _ in range(6):
-        q = np.concatenate([np.array(head, dtype=np.uint32), singles[:n], noise])
-        r = _records(p, q)
-        if r == target:
-            break
-        n += target - r
-    assert r == target and 0 < n <= len(singles), (r, target, n)
-    rng.shuffle(q)
-    return q
+_exact = functools.partial(wg.exact, _records)
 
 
 def test_record_counts_at_the_arrays_edges(edges):

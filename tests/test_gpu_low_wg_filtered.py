@@ -9,185 +9,50 @@ Every case goes through Pair.check under query_wg = 2, low_wg = 2 (results and e
 the path bits asserted, and is then run again under low_wg = 2 and under low_wg = 0 and compared byte for byte: results, scanned_blocks,
 scanned_docs, probes, hits, algorithmic_bytes, per-query blocks / docs and the growth of the context's scan histograms (nothing
 unbucketed).  The groups are tiny (group_packed = 1, FPX_DIRECT_MIN_ITEMS = 0), one at a time: each case is the smallest shape that
-reaches its branch.  The harness is test_gpu_low_wg.py's, copied."""
+reaches its branch.  The harness is wg_harness.py's, with this file's defaults below."""
+import functools
+
 import numpy as np
 import pytest
 
+import wg_harness as wg
+from wg_harness import (FILTERED, GROUP, LOW, QS_MAX_HASHES, QS_TASKS_FILT, QUERY_WG, TWO_PARTS, U64, HOT8, HOT1,
+                        aimed as _aimed, figures as _figures, legacy as _legacy, noise as _noise, post as _post, rand_items as _rand_items,
+                        rows as _rows, sampled as _sampled)
+
 pytestmark = pytest.mark.gpu
 
-SHARED, DOUBLE, HOT8, HOT1, CROWD, SINGLE, LISTS = 0x2BADF00D, 0x37770000, 0x4BCDEF01, 0x4CCDEF05, 0x51515151, 0x70000000, 0x19000000
-LOW, FILTERED, TWO_PARTS, QUERY_WG, GROUP, SECOND_TRIP = 4096, 256, 128, 64, 4, 2
+SHARED, DOUBLE, CROWD, SINGLE, LISTS = 0x2BADF00D, 0x37770000, 0x51515151, 0x70000000, 0x19000000
 TAKEN = LOW | FILTERED | QUERY_WG | GROUP
-QS_MAX_HASHES, QS_REC_CAP, QS_TASKS_FILT = 4096, 8192, 512
-U64 = np.uint64
 OPTIONS = ("low_wg", "hot_wg", "query_wg", "direct_min_items")
+_usual = wg.usual(SHARED, DOUBLE)
 
 
 @pytest.fixture(scope="module")
 def env():
-    from fpx_testlib import fpx, oracle, Pair
-    ctx = fpx.Context(0)
-    yield fpx, oracle, Pair, ctx
-    _reset(ctx)
-
-
-def _reset(ctx):
-    for name in OPTIONS:
-        ctx.set_option(name, -1)
-    ctx.set_option("group_packed", -2)
+    e = wg.open_context()
+    yield e
+    wg.reset(e[3], OPTIONS)
 
 
 @pytest.fixture
 def tiny(env, monkeypatch):
     """every file segment a direct-addressed candidate unless a test says otherwise, groups packed"""
-    fpx, oracle, Pair, ctx = env
-    monkeypatch.setenv("FPX_DIRECT_MIN_ITEMS", "0")
-    _reset(ctx)
-    ctx.set_option("group_packed", 1)
-    try:
-        yield fpx, oracle, Pair, ctx
-    finally:
-        _reset(ctx)
+    with wg.settings(env, monkeypatch, OPTIONS, group_packed=1) as e:
+        yield e
 
 
-def _post(hash_, ids):
-    return (U64(hash_) << U64(32)) | np.asarray(ids, dtype=U64)
-
-
-def _rand_items(rng, ids, nh, extra=()):
-    docs = np.asarray(ids, dtype=U64)
-    h = rng.integers(0, 1 << 32, (len(docs), nh), dtype=U64)
-    return np.unique(np.concatenate([((h << U64(32)) | docs[:, None]).ravel()] + [_post(hh, d) for hh, d in extra]))
-
-
-def _rows(items, doc):
-    return (items[(items & U64(0xFFFFFFFF)) == U64(doc)] >> U64(32)).astype(np.uint32)
-
-
-def _noise(rng, n):
-    return rng.integers(0, 1 << 32, n, dtype=U64).astype(np.uint32)
-
-
-class World:
+def World(Pair, ctx):
     """a Pair whose file segments meet in ONE packed group; checkpoints, a merged segment and memory segments next to it.  Snapshots are
     made under query_wg = 2: a filtered group may be part 0 of a snapshot in two parts"""
-
-    def __init__(self, Pair, ctx):
-        self.p, self.ctx, self.items, self.commit = Pair(ctx), ctx, [], 1
-
-    def file(self, items, ids, form="column", alive=None):
-        self.ctx.set_option("direct_min_items", (1 << 20) if form == "blocks" else 0)
-        ids = np.asarray(ids, dtype=np.uint32)
-        self.p.add_file(items, int(ids.min()), int(ids.max()), self.commit, ids, alive)
-        self.items.append(items)
-        self.commit += 1
-
-    def columns(self, rng, cols, per, nh, extra=lambda s, ids: [], first=1, again=None):
-        """again: {doc of an older column: the hashes the NEWEST column writes it again with (None: its own, all of them)}"""
-        for s in range(cols):
-            ids = np.arange(first + s * per, first + (s + 1) * per, dtype=np.int64)
-            items = _rand_items(rng, ids, nh, extra(s, ids))
-            if s == cols - 1 and again:
-                for d, hashes in again.items():
-                    old = next(it for it in self.items if len(_rows(it, d)))
-                    items = np.unique(np.concatenate([items, _post(0, [d]) | (np.asarray(_rows(old, d) if hashes is None else hashes, dtype=U64) << U64(32))]))
-                ids = np.array(sorted(list(ids) + list(again)), dtype=np.int64)
-            self.file(items, ids)
-        self.finish()
-        assert all(g.grouped for g in self.p.gpu_segs[:cols]), [g.layout_reason for g in self.p.gpu_segs]
-        info = self.p.gpu_segs[0].group_info()
-        assert info["packed"] == 1 and info["columns"] == cols and info["line_columns"] == (8 if cols <= 8 else 16), info
-        return self.p, first + cols * per
-
-    def memory(self, items, ids):
-        ids = np.asarray(ids, dtype=np.uint32)
-        self.p.add_memory(items, int(ids.min()), int(ids.max()), self.commit, ids)
-        self.items.append(items)
-        self.commit += 1
-
-    def changes(self, changes):
-        self.p.add_memory_changes(changes, self.commit)
-        self.commit += 1
-
-    def finish(self):
-        self.ctx.set_option("direct_min_items", -1)
-        self.ctx.set_option("query_wg", 2)                     # (the value in force when the snapshot is made)
-        try:
-            self.p.finish()
-        finally:
-            self.ctx.set_option("query_wg", -1)
-        return self.p
-
-
-def _aimed(rng, items, qlen, extra=()):
-    """a query of `qlen` hashes: a random doc's of `items` (half the query at most), `extra`, the rest noise"""
-    doc = items[rng.integers(0, len(items))] & U64(0xFFFFFFFF)
-    parts = [_rows(items, doc)[:max(1, qlen // 2)], np.asarray(extra, dtype=np.uint32)]
-    have = sum(len(x) for x in parts)
-    if qlen > have:
-        parts.append(_noise(rng, qlen - have))
-    q = np.concatenate(parts)
-    rng.shuffle(q)
-    return q
-
-
-def _sampled(rng, items, n):
-    """the hashes of `n` postings drawn from `items`: about n docs with a score of 1, a few with 2"""
-    return (items[rng.choice(len(items), n, replace=False)] >> U64(32)).astype(np.uint32)
-
-
-def _hist(ctx):
-    h, unb = ctx.scan_histograms()
-    return h.as_dict(), unb
-
-
-def _growth(a, b):
-    return {k: ([y - x for x, y in zip(a[k], b[k])] if isinstance(a[k], list) else b[k] - a[k]) for k in a}
-
-
-def _figures(s):
-    return (s.scanned_blocks, s.scanned_docs, s.probes, s.hits, s.algorithmic_bytes)
+    return wg.World(Pair, ctx, packed=1, snapshot_query_wg=2)
 
 
 def _both(ctx, p, queries, opts, want=TAKEN, want_not=0, query_wg=2):
-    """Pair.check under query_wg = 2, low_wg = 2 with the path bits asserted, then the batch under low_wg 2 and under 0, everything equal"""
-    try:
-        ctx.set_option("query_wg", query_wg)
-        ctx.set_option("low_wg", 2)
-        got, st = p.check(queries, opts)
-        print(f"low_wg 2: path_flags {st.path_flags}, blocks / docs / probes / hits / bytes {_figures(st)}")
-        assert st.path_flags & want == want and not st.path_flags & want_not, (st.path_flags, want, want_not)
-        h0, _ = _hist(ctx)
-        g1, s1, qb1, qd1 = p.reader.search_batch_stats(queries, opts)
-        h1, unb1 = _hist(ctx)
-        ctx.set_option("low_wg", 0)
-        g0, s0, qb0, qd0 = p.reader.search_batch_stats(queries, opts)
-        h2, unb2 = _hist(ctx)
-    finally:
-        ctx.set_option("low_wg", -1)
-        ctx.set_option("query_wg", -1)
-    print(f"low_wg 0: path_flags {s0.path_flags}, {_figures(s0)}; low_wg 2 again: {s1.path_flags}, {_figures(s1)}")
-    assert not s0.path_flags & LOW, s0.path_flags
-    if want & LOW:
-        assert not s0.path_flags & QUERY_WG, s0.path_flags         # (a batch with a low floor: the pipeline's, as before)
-    assert s1.path_flags & want == want and not s1.path_flags & want_not, (s1.path_flags, want, want_not)
-    assert g1 == got and g0 == got
-    assert _figures(s1) == _figures(s0), (_figures(s1), _figures(s0))
-    assert _figures(s1) == _figures(st), (_figures(s1), _figures(st))
-    assert [int(x) for x in qb1] == [int(x) for x in qb0] and [int(x) for x in qd1] == [int(x) for x in qd0]
-    assert _growth(h0, h1) == _growth(h1, h2), (_growth(h0, h1), _growth(h1, h2))
-    assert unb1 == 0 and unb2 == 0, (unb1, unb2)
-    return got, st
-
-
-def _legacy(fpx):
-    """the legacy protocol's search (src/legacy.zig:192-197)"""
-    return fpx.SearchOptions(max_results=500, min_score=1, min_score_pct=10)
-
-
-def _usual(s, ids):
-    """SHARED a list of 2 / 3 / 4 / 70 docs, DOUBLE a double in every column"""
-    return [(SHARED, ids[: [2, 3, 4, 70][s % 4]]), (DOUBLE, ids[:2])]
+    """Pair.check under query_wg = 2, low_wg = 2 with the path bits asserted, then the batch under low_wg 2 and under 0, everything equal.
+    Under 0 a batch with a low floor is the pipeline's, as before: bit 6 clear as well"""
+    return wg.both(ctx, p, queries, opts, "low_wg", 2, clear=LOW | (QUERY_WG if want & LOW else 0), want=want, want_not=want_not,
+                   also=(("query_wg", query_wg),), compare=wg.WITH_BYTES)      # (algorithmic_bytes too)
 
 
 # ---- 1. the legacy protocol on a group with a superseded doc -------------------------------------------------------------------------
@@ -507,19 +372,7 @@ def _records(p, q):
     return sum(s for _, s in p.osnap.search(q, 1 << 20, 1, 0))
 
 
-def _exact(p, rng, head, singles, target):
-    """a query of exactly `target` records: `head`, then hashes of one doc each (one of them may be some other doc's too), fifty of noise"""
-    noise = _noise(rng, 50)
-    n = target - 1000 * 8 * (HOT8 in head) - 1000 * (HOT1 in head)
-    for _ in range(6):
-        q = np.concatenate([np.array(head, dtype=np.uint32), singles[:n], noise])
-        r = _records(p, q)
-        if r == target:
-            break
-        n += target - r
-    assert r == target and 0 < n <= len(singles), (r, target, n)
-    rng.shuffle(q)
-    return q
+_exact = functools.partial(wg.exact, _records)
 
 
 def test_record_counts_at_the_arrays_edges(edges):

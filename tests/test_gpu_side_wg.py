@@ -8,134 +8,52 @@ growth of the context's scan histograms (nothing unbucketed).  The shapes are th
 import numpy as np
 import pytest
 
+import wg_harness as wg
+from wg_harness import QS_MAX_HASHES, QUERY_WG, SECOND_TRIP, SIDE, TWO_PARTS, U64, aimed as _aimed, rand_items as _rand_items
+
 pytestmark = pytest.mark.gpu
 
 HOT, SHARED, CROWD = 0x12345678, 0x0BADF00D, 0x51515151
-SIDE, TWO_PARTS, QUERY_WG, SECOND_TRIP = 512, 128, 64, 2
-QS_MAX_HASHES = 4096
-U64 = np.uint64
+OPTIONS = ("side_wg", "query_wg", "direct_min_items")
 
 
 @pytest.fixture(scope="module")
 def env():
-    from fpx_testlib import fpx, oracle, Pair
-    ctx = fpx.Context(0)
-    yield fpx, oracle, Pair, ctx
-    _reset(ctx)
-
-
-def _reset(ctx):
-    for name in ("side_wg", "query_wg", "direct_min_items"):
-        ctx.set_option(name, -1)
-    ctx.set_option("group_packed", -2)
+    e = wg.open_context()
+    yield e
+    wg.reset(e[3], OPTIONS)
 
 
 @pytest.fixture
 def live(env, monkeypatch):
     """every file segment a direct-addressed candidate unless a test says otherwise, groups packed; the options reset afterwards"""
-    fpx, oracle, Pair, ctx = env
-    monkeypatch.setenv("FPX_DIRECT_MIN_ITEMS", "0")
-    _reset(ctx)
-    ctx.set_option("group_packed", 1)
-    try:
-        yield fpx, oracle, Pair, ctx
-    finally:
-        _reset(ctx)
+    with wg.settings(env, monkeypatch, OPTIONS, group_packed=1) as e:
+        yield e
 
 
-def _post(hash_, ids):
-    return (U64(hash_) << U64(32)) | np.asarray(ids, dtype=U64)
-
-
-def _rand_items(rng, first, per, nh, extra=(), lo=0, hi=1 << 32):
-    docs = np.arange(first, first + per, dtype=U64)
-    h = rng.integers(lo, hi, (per, nh), dtype=U64)
-    return np.unique(np.concatenate([((h << U64(32)) | docs[:, None]).ravel()] + [_post(hh, ids) for hh, ids in extra]))
-
-
-class World:
-    """a Pair filled the way a live index grows: a packed group, checkpoints in blocks (small decoded), merged segments that are
-    direct-addressed alone, memory segments"""
+class World(wg.World):
+    """a Pair filled the way a live index grows: a packed group, checkpoints in blocks (small decoded: what file() takes a segment for
+    unless told), merged segments that are direct-addressed alone, memory segments"""
 
     def __init__(self, Pair, ctx):
-        self.p, self.ctx, self.items, self.commit = Pair(ctx), ctx, [], 1
+        super().__init__(Pair, ctx, packed=1, form="blocks")
 
     def group(self, rng, cols, per, nh, first=1):
+        """`cols` columns with SHARED a list of 2 / 3 / 4 / 70 docs, met in a snapshot: a packed group -> the first free doc.  (In place of
+        the harness's columns() + group(): direct_min_items is set once, and every segment there is must be in the group)"""
         self.ctx.set_option("direct_min_items", 0)
         for s in range(cols):
-            f = first + s * per
-            it = _rand_items(rng, f, per, nh, [(SHARED, np.arange(f, f + [2, 3, 4, 70][s % 4]))])
-            self.file(it, np.arange(f, f + per), form=None)
-        self.p.finish()                                       # (the columns meet in a snapshot: a packed group)
+            ids = np.arange(first + s * per, first + (s + 1) * per)
+            self.file(_rand_items(rng, ids, nh, [(SHARED, ids[: [2, 3, 4, 70][s % 4]])]), ids, form=None)
+        self.p.finish()
         assert all(g.grouped for g in self.p.gpu_segs), [g.layout_reason for g in self.p.gpu_segs]
         return first + cols * per
-
-    def file(self, items, ids, alive=None, form="blocks", block_size=512):
-        if form is not None:
-            self.ctx.set_option("direct_min_items", (1 << 20) if form == "blocks" else 0)
-        ids = np.asarray(ids, dtype=np.uint32)
-        self.p.add_file(items, int(ids.min()), int(ids.max()), self.commit, ids, alive, block_size=block_size)
-        self.items.append(items)
-        self.commit += 1
-
-    def memory(self, items, ids):
-        ids = np.asarray(ids, dtype=np.uint32)
-        self.p.add_memory(items, int(ids.min()), int(ids.max()), self.commit, ids)
-        self.items.append(items)
-        self.commit += 1
-
-    def finish(self):
-        self.ctx.set_option("direct_min_items", -1)
-        self.p.finish()
-        return self.p
-
-
-def _aimed(rng, items, qlen, extra=()):
-    """a query of `qlen` hashes: half of them a random doc's of `items`, `extra`, the rest noise"""
-    doc = items[rng.integers(0, len(items))] & U64(0xFFFFFFFF)
-    own = (items[(items & U64(0xFFFFFFFF)) == doc] >> U64(32)).astype(np.uint32)[:max(1, qlen // 2)]
-    parts = [own, np.asarray(extra, dtype=np.uint32)]
-    have = sum(len(x) for x in parts)
-    if qlen > have:
-        parts.append(rng.integers(0, 1 << 32, qlen - have, dtype=U64).astype(np.uint32))
-    q = np.concatenate(parts)
-    rng.shuffle(q)
-    return q
-
-
-def _hist(ctx):
-    h, unb = ctx.scan_histograms()
-    return h.as_dict(), unb
-
-
-def _growth(a, b):
-    return {k: ([y - x for x, y in zip(a[k], b[k])] if isinstance(a[k], list) else b[k] - a[k]) for k in a}
 
 
 def _both(ctx, p, queries, opts, want=0, want_not=0):
     """Pair.check under side_wg = 1 with the path bits asserted, then the batch under side_wg = 1 and 0, everything equal"""
-    try:
-        ctx.set_option("side_wg", 1)
-        got, st = p.check(queries, opts)
-        assert st.path_flags & want == want and not st.path_flags & want_not, (st.path_flags, want, want_not)
-        h0, _ = _hist(ctx)
-        g1, s1, qb1, qd1 = p.reader.search_batch_stats(queries, opts)
-        h1, unb1 = _hist(ctx)
-        ctx.set_option("side_wg", 0)
-        g0, s0, qb0, qd0 = p.reader.search_batch_stats(queries, opts)
-        h2, unb2 = _hist(ctx)
-    finally:
-        ctx.set_option("side_wg", -1)
-    assert not s0.path_flags & SIDE, s0.path_flags
-    assert s1.path_flags & want == want and not s1.path_flags & want_not, (s1.path_flags, want, want_not)
-    assert g1 == got and g0 == got
-    assert (s1.scanned_blocks, s1.scanned_docs, s1.probes, s1.hits) == (s0.scanned_blocks, s0.scanned_docs, s0.probes, s0.hits), \
-        ((s1.scanned_blocks, s1.scanned_docs, s1.probes, s1.hits), (s0.scanned_blocks, s0.scanned_docs, s0.probes, s0.hits))
-    assert (s1.scanned_blocks, s1.scanned_docs, s1.probes, s1.hits) == (st.scanned_blocks, st.scanned_docs, st.probes, st.hits)
-    assert [int(x) for x in qb1] == [int(x) for x in qb0] and [int(x) for x in qd1] == [int(x) for x in qd0]
-    assert _growth(h0, h1) == _growth(h1, h2), (_growth(h0, h1), _growth(h1, h2))
-    assert unb1 == 0 and unb2 == 0, (unb1, unb2)
-    return got, st
+    return wg.both(ctx, p, queries, opts, "side_wg", 1, clear=SIDE, want=want, want_not=want_not,
+                   compare=wg.FOUR)      # (blocks, docs, probes and hits: this suite never compared algorithmic_bytes)
 
 
 def _option_sets(fpx):
@@ -150,14 +68,14 @@ def _two_part_world(Pair, ctx, rng):
     nxt = w.group(rng, 4, 3000, 40)
     for s in range(3):
         ids = np.arange(nxt, nxt + 1000)
-        w.file(_rand_items(rng, nxt, 1000, 48, [(SHARED, ids[:7]), (HOT, ids[:600])]), ids)
+        w.file(_rand_items(rng, ids, 48, [(SHARED, ids[:7]), (HOT, ids[:600])]), ids)
         nxt += 1000
     ids = np.arange(nxt, nxt + 2500)
-    w.file(_rand_items(rng, nxt, 2500, 48, [(SHARED, ids[:70])]), ids, form="alone")
+    w.file(_rand_items(rng, ids, 48, [(SHARED, ids[:70])]), ids, form="alone")
     nxt += 2500
     for m in range(3):
         ids = np.arange(nxt, nxt + 60)
-        w.memory(_rand_items(rng, nxt, 60, 48, [(SHARED, ids[:3])]), ids)
+        w.memory(_rand_items(rng, ids, 48, [(SHARED, ids[:3])]), ids)
         nxt += 60
     return w, w.finish()
 
@@ -198,10 +116,10 @@ def test_a_whole_snapshot_of_side_segments_only(live):
     nxt = 1
     for s in range(2):
         ids = np.arange(nxt, nxt + 1000)
-        w.file(_rand_items(rng, nxt, 1000, 48, [(SHARED, ids[:5])]), ids)
+        w.file(_rand_items(rng, ids, 48, [(SHARED, ids[:5])]), ids)
         nxt += 1000
     ids = np.arange(nxt, nxt + 1500)
-    w.file(_rand_items(rng, nxt, 1500, 48, [(SHARED, ids[:9])]), ids, form="alone")
+    w.file(_rand_items(rng, ids, 48, [(SHARED, ids[:9])]), ids, form="alone")
     p = w.finish()
     assert [bool(g.direct) for g in p.gpu_segs] == [False, False, True] and not any(g.grouped for g in p.gpu_segs)
     queries = [_aimed(rng, w.items[i % 3], [1000, 300, 64, 1500][i % 4], [SHARED]) for i in range(40)]
@@ -217,12 +135,12 @@ def test_the_caps_and_the_list_forms(live):
     rng = np.random.default_rng(810)
     w = World(Pair, ctx)
     ids = np.arange(1, 2001)
-    w.file(_rand_items(rng, 1, 2000, 8, [(HOT, ids[:1500]), (SHARED, ids[:2])]), ids, block_size=64)
+    w.file(_rand_items(rng, ids, 8, [(HOT, ids[:1500]), (SHARED, ids[:2])]), ids, block_size=64)
     ids = np.arange(2001, 5201)
-    w.file(_rand_items(rng, 2001, 3200, 24, [(HOT + 1, ids[:3000]), (SHARED, ids[:5])]), ids)
+    w.file(_rand_items(rng, ids, 24, [(HOT + 1, ids[:3000]), (SHARED, ids[:5])]), ids)
     ids = np.arange(5201, 7201)
     lists = [(0x0BADF002, ids[:2]), (0x0BADF003, ids[:3]), (0x0BADF004, ids[:4]), (0x0BADF070, ids[:70]), (HOT, ids[:1200])]
-    w.file(_rand_items(rng, 5201, 2000, 32, lists), ids, form="alone")
+    w.file(_rand_items(rng, ids, 32, lists), ids, form="alone")
     p = w.finish()
     assert [bool(g.direct) for g in p.gpu_segs] == [False, False, True]
     special = [HOT, HOT + 1, SHARED, 0x0BADF002, 0x0BADF003, 0x0BADF004, 0x0BADF070]
@@ -242,22 +160,22 @@ def test_superseded_docs_among_the_side_segments(live):
     nxt = w.group(rng, 4, 3000, 40)
     c0 = np.arange(nxt, nxt + 1000)
     rewritten, tombstoned = int(c0[17]), int(c0[99])
-    w.file(_rand_items(rng, nxt, 1000, 48), c0)
+    w.file(_rand_items(rng, c0, 48), c0)
     nxt += 1000
     ids = np.concatenate([[tombstoned], np.arange(nxt, nxt + 1000)])
-    w.file(_rand_items(rng, nxt, 1000, 48), ids, alive=np.array([0] + [1] * 1000, dtype=np.uint8))
+    w.file(_rand_items(rng, ids[1:], 48), ids, alive=np.array([0] + [1] * 1000, dtype=np.uint8))
     nxt += 1000
     ids = np.concatenate([[rewritten], np.arange(nxt, nxt + 1000)])
     new_rows = (rng.integers(0, 1 << 32, 48, dtype=U64) << U64(32)) | U64(rewritten)
-    w.file(np.unique(np.concatenate([_rand_items(rng, nxt, 1000, 48), new_rows])), ids)
+    w.file(np.unique(np.concatenate([_rand_items(rng, ids[1:], 48), new_rows])), ids)
     nxt += 1000
     merged = np.arange(nxt, nxt + 2500)
     moved = int(merged[5])
-    w.file(_rand_items(rng, nxt, 2500, 48), merged, form="alone")
+    w.file(_rand_items(rng, merged, 48), merged, form="alone")
     nxt += 2500
     ids = np.concatenate([[moved], np.arange(nxt, nxt + 60)])
     moved_rows = (rng.integers(0, 1 << 32, 48, dtype=U64) << U64(32)) | U64(moved)
-    w.memory(np.unique(np.concatenate([_rand_items(rng, nxt, 60, 48), moved_rows])), ids)
+    w.memory(np.unique(np.concatenate([_rand_items(rng, ids[1:], 48), moved_rows])), ids)
     p = w.finish()
 
     def rows(items, doc):
@@ -285,11 +203,11 @@ def test_edge_queries(live):
     rng = np.random.default_rng(812)
     w = World(Pair, ctx)
     ids = np.arange(1, 1001)
-    w.file(_rand_items(rng, 1, 1000, 48, [(0, ids[:2]), (0xFFFFFFFF, ids[5:8])]), ids)
+    w.file(_rand_items(rng, ids, 48, [(0, ids[:2]), (0xFFFFFFFF, ids[5:8])]), ids)
     ids = np.arange(1001, 2001)
-    w.file(_rand_items(rng, 1001, 1000, 48, lo=0x20000000, hi=0xE0000000), ids)
+    w.file(_rand_items(rng, ids, 48, lo=0x20000000, hi=0xE0000000), ids)
     ids = np.arange(2001, 4001)
-    w.file(_rand_items(rng, 2001, 2000, 48, lo=0x10000000, hi=0xF0000000), ids, form="alone")
+    w.file(_rand_items(rng, ids, 48, lo=0x10000000, hi=0xF0000000), ids, form="alone")
     p = w.finish()
     # hashes absent from the second checkpoint: inside a block (the reference visits one block: a cell of code 1 or an absent hash next
     # to items), in the gap between two blocks where there is one, and outside every block (no visit: code 2) -- by the oracle's count
@@ -337,9 +255,9 @@ def test_crowded_queries_take_the_shared_list(live):
     rng = np.random.default_rng(813)
     w = World(Pair, ctx)
     ids = np.arange(1, 1501)
-    w.file(_rand_items(rng, 1, 1500, 40, [(CROWD + k * 7919, ids[100:350]) for k in range(30)]), ids)
+    w.file(_rand_items(rng, ids, 40, [(CROWD + k * 7919, ids[100:350]) for k in range(30)]), ids)
     ids = np.arange(1501, 3001)
-    w.file(_rand_items(rng, 1501, 1500, 40, [(CROWD + k * 7919, ids[:20]) for k in range(30)]), ids, form="alone")
+    w.file(_rand_items(rng, ids, 40, [(CROWD + k * 7919, ids[:20]) for k in range(30)]), ids, form="alone")
     p = w.finish()
     crowd = np.array([CROWD + k * 7919 for k in range(30)], dtype=np.uint32)
     queries = []
@@ -362,7 +280,7 @@ def test_records_beyond_the_lds_array_are_handed_back(live):
     hots = [0x40000000 + 977 * k for k in range(12)]
     for s in range(3):
         ids = np.arange(nxt, nxt + 2000)
-        w.file(_rand_items(rng, nxt, 2000, 24, [(k, ids[:1500]) for k in hots[s::3]]), ids)
+        w.file(_rand_items(rng, ids, 24, [(k, ids[:1500]) for k in hots[s::3]]), ids)
         nxt += 2000
     p = w.finish()
     plain = [_aimed(rng, w.items[4 + i % 3], 1000) for i in range(16)]
@@ -394,10 +312,10 @@ def test_a_second_group_in_part_one_is_not_eligible(live):
     nxt = w.group(rng, 5, 3000, 40)
     for s in range(2):
         ids = np.arange(nxt, nxt + 900)
-        w.file(_rand_items(rng, nxt, 900, 40, [(SHARED, ids[:11])]), ids, form="alone")
+        w.file(_rand_items(rng, ids, 40, [(SHARED, ids[:11])]), ids, form="alone")
         nxt += 900
     ids = np.arange(nxt, nxt + 500)
-    w.file(_rand_items(rng, nxt, 500, 40), ids)
+    w.file(_rand_items(rng, ids, 40), ids)
     p = w.finish()
     infos = [g.group_info() for g in p.gpu_segs[:7]]
     assert all(i is not None for i in infos) and infos[5]["columns"] == 2, infos
@@ -413,9 +331,9 @@ def test_doc_ids_at_the_top_of_the_range(live):
     w = World(Pair, ctx)
     w.group(rng, 4, 3000, 40)
     top = np.arange(0xFFFFFF00, 0x100000000, dtype=np.int64)
-    w.file(_rand_items(rng, 0xFFFFFF00, 256, 48, [(SHARED, top[-5:]), (HOT, top[:200])]), top)
+    w.file(_rand_items(rng, top, 48, [(SHARED, top[-5:]), (HOT, top[:200])]), top)
     sign = np.arange(0x7FFFFF00, 0x80000100, dtype=np.int64)
-    w.file(_rand_items(rng, 0x7FFFFF00, 512, 48, [(SHARED, sign[250:262]), (HOT, sign[200:300])]), sign, form="alone")
+    w.file(_rand_items(rng, sign, 48, [(SHARED, sign[250:262]), (HOT, sign[200:300])]), sign, form="alone")
     p = w.finish()
     assert bool(p.gpu_segs[5].direct) and not p.gpu_segs[5].grouped and not p.gpu_segs[4].direct
 

@@ -10,22 +10,21 @@ the floor is 5: exactly N candidates, for
 
 all as queries of ONE batch, with aimed queries between them -- a batch of more queries than the chip holds workgroups (four per CU), in
 cycles of nine, so that a workgroup takes several queries and meets a different N each time: what one query leaves in the workgroup's
-state the next one finds.  The worlds are built by the two files' own builders."""
+state the next one finds.  The worlds are wg_harness.py's, with the two files' settings."""
 import numpy as np
 import pytest
 
-import test_gpu_side_wg as side_t
-import test_gpu_words_wg as words_t
-from test_gpu_words_wg import _figures
+import wg_harness as wg
+from wg_harness import U64, WORDS_LO, WORDS_HI, aimed, figures as _figures, rand_items
 
 pytestmark = pytest.mark.gpu
 
 NS = (4, 5, 32, 33, 192, 193, 300)
-KERNELS = {"side": ("side_wg", 512), "words": ("words_wg", 2048)}      # the option, the kernel's bit of fpx_stats.path_flags
-SECOND_TRIP = 2
+KERNELS = {"side": ("side_wg", wg.SIDE), "words": ("words_wg", wg.WORDS)}      # the option, the kernel's bit of fpx_stats.path_flags
+SECOND_TRIP = wg.SECOND_TRIP
 BATCH, CYCLE = 1200, 9                # (CYCLE: the seven N and two aimed queries; 9 divides no grid of 4 x a power of two)
 SEED = 1600                           # (with it the oracle alone gives every N-doc query exactly N results: checked before this was committed)
-U64 = np.uint64
+OPTIONS = ("words_wg", "side_wg", "query_wg", "direct_min_items")
 
 
 def _five(n):
@@ -44,22 +43,22 @@ def _shared_rows(ids):
 
 def side_world(Pair, ctx, rng):
     """a young index: two checkpoints in blocks (small decoded), one segment direct-addressed alone; the shared hashes in the first"""
-    w = side_t.World(Pair, ctx)
+    w = wg.World(Pair, ctx, packed=1, form="blocks")
     ids = np.arange(1, 1501)
-    w.file(side_t._rand_items(rng, 1, 1500, 40, _shared_rows(ids)), ids)
-    w.file(side_t._rand_items(rng, 1501, 1000, 40), np.arange(1501, 2501))
-    w.file(side_t._rand_items(rng, 2501, 1500, 40), np.arange(2501, 4001), form="alone")
+    w.file(rand_items(rng, ids, 40, _shared_rows(ids)), ids)
+    w.file(rand_items(rng, np.arange(1501, 2501), 40), np.arange(1501, 2501))
+    w.file(rand_items(rng, np.arange(2501, 4001), 40), np.arange(2501, 4001), form="alone")
     return w, w.finish()
 
 
 def words_world(Pair, ctx, rng):
     """one group of four columns in directory + words form; the shared hashes in column 0"""
-    w = words_t.World(Pair, ctx)
+    w = wg.World(Pair, ctx, packed=0, lo=WORDS_LO, hi=WORDS_HI)
     p, _ = w.columns(rng, 4, 1200, 40, lambda s, ids: _shared_rows(ids) if s == 0 else [])
     return w, p
 
 
-def make_queries(rng, items, aimed):
+def make_queries(rng, items):
     """BATCH queries in cycles of nine: the seven N-doc queries and two aimed ones, every other cycle aimed ones only (the batch's
     candidates stay below the shared list's first size, 64 per query: more would hand the batch back).  -> the queries, {position: N}"""
     of_n = {}
@@ -79,10 +78,9 @@ def make_queries(rng, items, aimed):
 
 @pytest.fixture(scope="module")
 def env():
-    from fpx_testlib import fpx, oracle, Pair
-    ctx = fpx.Context(0)
-    yield fpx, oracle, Pair, ctx
-    words_t._reset(ctx)
+    e = wg.open_context()
+    yield e
+    wg.reset(e[3], OPTIONS)
 
 
 @pytest.mark.parametrize("kernel", sorted(KERNELS))
@@ -90,12 +88,12 @@ def test_the_tail_at_its_thresholds(env, monkeypatch, kernel):
     fpx, oracle, Pair, ctx = env
     option, bit = KERNELS[kernel]
     monkeypatch.setenv("FPX_DIRECT_MIN_ITEMS", "0")
-    words_t._reset(ctx)
+    wg.reset(ctx, OPTIONS)
     ctx.set_option("group_packed", 1 if kernel == "side" else 0)
     rng = np.random.default_rng(SEED)
     try:
         w, p = (side_world if kernel == "side" else words_world)(Pair, ctx, rng)
-        queries, where = make_queries(rng, w.items, side_t._aimed if kernel == "side" else words_t._aimed)
+        queries, where = make_queries(rng, w.items)
         opts = fpx.SearchOptions(max_results=max(NS), min_score=5, min_score_pct=0)
         four = next(i for i, n in where.items() if n == 4)
         assert sum(where.values()) < 1 << 16 and set(where.values()) == set(NS)  # (the shared list takes the batch's candidates: nothing is handed back)
@@ -105,7 +103,7 @@ def test_the_tail_at_its_thresholds(env, monkeypatch, kernel):
         ctx.set_option(option, 0)
         got0, st0 = p.reader.search_batch(queries, opts)
     finally:
-        words_t._reset(ctx)
+        wg.reset(ctx, OPTIONS)
     print(f"{kernel}: {option} 1: path_flags {st.path_flags}, {_figures(st)}; 0: {st0.path_flags}, {_figures(st0)}; N = 4 alone: {st_four.path_flags}")
     assert st.path_flags & bit and st.path_flags & SECOND_TRIP, st.path_flags
     assert not st0.path_flags & bit, st0.path_flags

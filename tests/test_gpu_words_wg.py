@@ -7,166 +7,52 @@ Every case goes through Pair.check under the option (results and every query's s
 again under the option and under words_wg = 0 and compared byte for byte: results, scanned_blocks, scanned_docs, probes, hits,
 algorithmic_bytes, per-query blocks / docs and the growth of the context's scan histograms (nothing unbucketed).  The groups are tiny
 (group_packed = 0, FPX_DIRECT_MIN_ITEMS = 0): each case is the smallest shape that reaches a branch of the kernel."""
+import functools
+
 import numpy as np
 import pytest
+
+import wg_harness as wg
+from wg_harness import (FILTERED, GROUP, QS_MAX_HASHES, QUERY_WG, SECOND_TRIP, SIDE, TWO_PARTS, U64, WORDS, WORDS_LO as LO, WORDS_HI as HI,
+                        aimed as _aimed, figures as _figures, rows as _rows)
 
 pytestmark = pytest.mark.gpu
 
 SHARED, DOUBLE, BIG, HOT, CROWD, LINE = 0x2BADF00D, 0x37770000, 0x42345678, 0x4BCDEF01, 0x51515151, 0x5A5A5A00
-WORDS, FILTERED, TWO_PARTS, QUERY_WG, SIDE, GROUP, SECOND_TRIP = 2048, 256, 128, 64, 512, 4, 2
-QS_MAX_HASHES = 4096
-U64 = np.uint64
-LO, HI = 0x10000000, 0xF0000000          # the columns' random hashes: noise below and above is out of every column's range
 OPTIONS = ("words_wg", "side_wg", "query_wg", "direct_min_items")
+_usual = wg.usual(SHARED, DOUBLE)
+_reset = functools.partial(wg.reset, options=OPTIONS)
+_rand_items = functools.partial(wg.rand_items, lo=LO, hi=HI)      # (the columns' random hashes are in [LO, HI) unless a test says otherwise)
 
 
 @pytest.fixture(scope="module")
 def env():
-    from fpx_testlib import fpx, oracle, Pair
-    ctx = fpx.Context(0)
-    yield fpx, oracle, Pair, ctx
-    _reset(ctx)
-
-
-def _reset(ctx):
-    for name in OPTIONS:
-        ctx.set_option(name, -1)
-    ctx.set_option("group_packed", -2)
+    e = wg.open_context()
+    yield e
+    _reset(e[3])
 
 
 @pytest.fixture
 def tiny(env, monkeypatch):
     """every file segment a direct-addressed candidate unless a test says otherwise, groups in directory + words form"""
-    fpx, oracle, Pair, ctx = env
-    monkeypatch.setenv("FPX_DIRECT_MIN_ITEMS", "0")
-    _reset(ctx)
-    ctx.set_option("group_packed", 0)
-    try:
-        yield fpx, oracle, Pair, ctx
-    finally:
-        _reset(ctx)
+    with wg.settings(env, monkeypatch, OPTIONS, group_packed=0) as e:
+        yield e
 
 
-def _post(hash_, ids):
-    return (U64(hash_) << U64(32)) | np.asarray(ids, dtype=U64)
-
-
-def _rand_items(rng, ids, nh, extra=(), lo=LO, hi=HI):
-    docs = np.asarray(ids, dtype=U64)
-    h = rng.integers(lo, hi, (len(docs), nh), dtype=U64)
-    return np.unique(np.concatenate([((h << U64(32)) | docs[:, None]).ravel()] + [_post(hh, d) for hh, d in extra]))
-
-
-def _rows(items, doc):
-    return (items[(items & U64(0xFFFFFFFF)) == U64(doc)] >> U64(32)).astype(np.uint32)
-
-
-class World:
+def World(Pair, ctx):
     """a Pair whose file segments meet in ONE group in directory + words form; checkpoints, a merged segment and memory segments next to it"""
-
-    def __init__(self, Pair, ctx):
-        self.p, self.ctx, self.items, self.index, self.commit = Pair(ctx), ctx, [], [], 1
-
-    def file(self, items, ids, alive=None, form="column", block_size=512):
-        self.ctx.set_option("direct_min_items", (1 << 20) if form == "blocks" else 0)
-        ids = np.asarray(ids, dtype=np.uint32)
-        _, index = self.p.add_file(items, int(ids.min()), int(ids.max()), self.commit, ids, alive, block_size=block_size)
-        self.items.append(items); self.index.append(index)
-        self.commit += 1
-
-    def columns(self, rng, cols, per, nh, extra=lambda s, ids: [], block_size=512, first=1, **kw):
-        for s in range(cols):
-            ids = np.arange(first + s * per, first + (s + 1) * per)
-            self.file(_rand_items(rng, ids, nh, extra(s, ids), **kw), ids, block_size=block_size)
-        return self.group(cols), first + cols * per
-
-    def group(self, cols):
-        """the columns meet in a snapshot: a group, not packed"""
-        self.p.finish()
-        assert all(g.grouped for g in self.p.gpu_segs[:cols]), [g.layout_reason for g in self.p.gpu_segs]
-        info = self.p.gpu_segs[0].group_info()
-        assert info["packed"] == 0 and info["columns"] == cols and info["line_columns"] == (8 if cols <= 8 else 16), info
-        return self.p
-
-    def memory(self, items, ids):
-        ids = np.asarray(ids, dtype=np.uint32)
-        self.p.add_memory(items, int(ids.min()), int(ids.max()), self.commit, ids)
-        self.items.append(items)
-        self.commit += 1
-
-    def finish(self):
-        self.ctx.set_option("direct_min_items", -1)
-        self.p.finish()
-        return self.p
-
-
-def _aimed(rng, items, qlen, extra=(), lo=None, hi=None):
-    """a query of `qlen` hashes: a random doc's of `items` (half the query at most), `extra`, the rest noise over the whole hash space
-    (half of it inside [lo, hi) where given)"""
-    doc = items[rng.integers(0, len(items))] & U64(0xFFFFFFFF)
-    parts = [_rows(items, doc)[:max(1, qlen // 2)], np.asarray(extra, dtype=np.uint32)]
-    have = sum(len(x) for x in parts)
-    if qlen > have:
-        parts.append(rng.integers(0, 1 << 32, qlen - have, dtype=U64).astype(np.uint32))
-        if lo is not None:
-            parts[-1][::2] = rng.integers(lo, hi, len(parts[-1][::2]), dtype=U64).astype(np.uint32)
-    q = np.concatenate(parts)
-    rng.shuffle(q)
-    return q
-
-
-def _hist(ctx):
-    h, unb = ctx.scan_histograms()
-    return h.as_dict(), unb
-
-
-def _growth(a, b):
-    return {k: ([y - x for x, y in zip(a[k], b[k])] if isinstance(a[k], list) else b[k] - a[k]) for k in a}
-
-
-def _figures(s):
-    return (s.scanned_blocks, s.scanned_docs, s.probes, s.hits, s.algorithmic_bytes)
+    return wg.World(Pair, ctx, packed=0, lo=LO, hi=HI)
 
 
 def _both(ctx, p, queries, opts, level=1, want=WORDS | GROUP, want_not=QUERY_WG, also=()):
     """Pair.check under words_wg = level with the path bits asserted, then the batch under the option and under 0, everything equal"""
-    try:
-        for name, value in also:
-            ctx.set_option(name, value)
-        ctx.set_option("words_wg", level)
-        got, st = p.check(queries, opts)
-        print(f"words_wg {level}: path_flags {st.path_flags}, blocks / docs / probes / hits / bytes {_figures(st)}")
-        assert st.path_flags & want == want and not st.path_flags & want_not, (st.path_flags, want, want_not)
-        h0, _ = _hist(ctx)
-        g1, s1, qb1, qd1 = p.reader.search_batch_stats(queries, opts)
-        h1, unb1 = _hist(ctx)
-        ctx.set_option("words_wg", 0)
-        g0, s0, qb0, qd0 = p.reader.search_batch_stats(queries, opts)
-        h2, unb2 = _hist(ctx)
-    finally:
-        ctx.set_option("words_wg", -1)
-        for name, _ in also:
-            ctx.set_option(name, -1)
-    print(f"words_wg 0: path_flags {s0.path_flags}, {_figures(s0)}; words_wg {level} again: {s1.path_flags}, {_figures(s1)}")
-    assert not s0.path_flags & WORDS, s0.path_flags
-    assert s1.path_flags & want == want and not s1.path_flags & want_not, (s1.path_flags, want, want_not)
-    assert g1 == got and g0 == got
-    assert _figures(s1) == _figures(s0), (_figures(s1), _figures(s0))
-    assert _figures(s1) == _figures(st), (_figures(s1), _figures(st))
-    assert [int(x) for x in qb1] == [int(x) for x in qb0] and [int(x) for x in qd1] == [int(x) for x in qd0]
-    assert _growth(h0, h1) == _growth(h1, h2), (_growth(h0, h1), _growth(h1, h2))
-    assert unb1 == 0 and unb2 == 0, (unb1, unb2)
-    return got, st
+    return wg.both(ctx, p, queries, opts, "words_wg", level, clear=WORDS, want=want, want_not=want_not, also=also,
+                   compare=wg.WITH_BYTES)      # (algorithmic_bytes too)
 
 
 def _option_sets(fpx):
     return [fpx.http_options(), fpx.SearchOptions(max_results=100, min_score=3, min_score_pct=0),
             fpx.SearchOptions(max_results=1, min_score=4, min_score_pct=100)]
-
-
-def _usual(s, ids):
-    """SHARED a list of 2 / 3 / 4 / 70 docs, DOUBLE a double in every column"""
-    return [(SHARED, ids[: [2, 3, 4, 70][s % 4]]), (DOUBLE, ids[:2])]
 
 
 def _gap_hashes(oracle, w, col, n=3):

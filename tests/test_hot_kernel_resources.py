@@ -1,28 +1,20 @@
 """What the compiler made of k_search_classes (csrc/fpx_qsearch.hpp), read from the built code object the way tests/test_kernel_resources.py
 reads k_search_query's: its four instantiations (8 / 16 columns x MEM) exist, none has a scratch segment or spills a vector register, and
 none is above 128 vector registers (the occupancy k_search_query's body was written for) -- no GPU needed."""
-import glob
-import os
 import re
 
 import pytest
 
-from test_kernel_resources import FIELDS, PKG, _notes      # (the same reader)
+import kernel_notes
 
 
 @pytest.fixture(scope="module")
 def classes():
-    lib = os.path.join(PKG, "libfpx.so")
-    search_o = os.path.join(PKG, "build", "fpx_search.o")
-    if not glob.glob(os.path.join(PKG, "build", "*.o")) and not os.path.exists(lib):
-        pytest.skip("nothing built: neither libfpx.so nor build/*.o")
-    notes = _notes(lib if os.path.exists(lib) else search_o)
     found = {}
-    for m in re.finditer(r"- \.agpr_count:.*?(?=\n\s+- \.agpr_count:|\namdhsa\.target|\Z)", notes, flags=re.S):
-        blk = m.group(0)
-        t = re.search(r"\.name:\s+_ZN3fpx16k_search_classesILi(\d+)ELb([01])EEEv", blk)
+    for name, figures in kernel_notes.kernels().items():
+        t = re.match(r"_ZN3fpx16k_search_classesILi(\d+)ELb([01])EEEv", name)
         if t:
-            found[(int(t.group(1)), bool(int(t.group(2))))] = {f: int(re.search(rf"\.{f}:\s+(\d+)", blk).group(1)) for f in FIELDS}      # NS, MEM
+            found[(int(t.group(1)), bool(int(t.group(2))))] = figures      # NS, MEM
     return found
 
 

@@ -4,33 +4,24 @@ sorted tail), read from the built code object the way tests/test_kernel_resource
 bytes at most -- with the dynamic 39 KB four workgroups share a CU --; and none has more scratch than k_search_query's FILTERED
 instantiation of the same (NS, QS, MEM) in the same code object, which tests/test_kernel_resources.py bounds at 88 / 24 bytes.  No GPU
 needed."""
-import glob
-import os
 import re
 
 import pytest
 
-from test_kernel_resources import FIELDS, PKG, _notes      # (the same reader)
+import kernel_notes
 
 
 @pytest.fixture(scope="module")
 def built():
     """({(NS, QS, MEM): k_search_low_filt's figures}, {(NS, QS, MEM): those of k_search_query<NS, QS, MEM, true>})"""
-    lib = os.path.join(PKG, "libfpx.so")
-    search_o = os.path.join(PKG, "build", "fpx_search.o")
-    if not glob.glob(os.path.join(PKG, "build", "*.o")) and not os.path.exists(lib):
-        pytest.skip("nothing built: neither libfpx.so nor build/*.o")
-    notes = _notes(lib if os.path.exists(lib) else search_o)
     low_filt, query_filt = {}, {}
-    for m in re.finditer(r"- \.agpr_count:.*?(?=\n\s+- \.agpr_count:|\namdhsa\.target|\Z)", notes, flags=re.S):
-        blk = m.group(0)
-        figures = lambda: {f: int(re.search(rf"\.{f}:\s+(\d+)", blk).group(1)) for f in FIELDS}
-        t = re.search(r"\.name:\s+_ZN3fpx17k_search_low_filtILi(\d+)ELb([01])ELb([01])EEEv", blk)
+    for name, figures in kernel_notes.kernels().items():
+        t = re.match(r"_ZN3fpx17k_search_low_filtILi(\d+)ELb([01])ELb([01])EEEv", name)
         if t:
-            low_filt[(int(t.group(1)), bool(int(t.group(2))), bool(int(t.group(3))))] = figures()       # NS, QS, MEM
-        t = re.search(r"\.name:\s+_ZN3fpx14k_search_queryILi(\d+)ELb([01])ELb([01])ELb1EEEv", blk)
+            low_filt[(int(t.group(1)), bool(int(t.group(2))), bool(int(t.group(3))))] = figures       # NS, QS, MEM
+        t = re.match(r"_ZN3fpx14k_search_queryILi(\d+)ELb([01])ELb([01])ELb1EEEv", name)
         if t:
-            query_filt[(int(t.group(1)), bool(int(t.group(2))), bool(int(t.group(3))))] = figures()
+            query_filt[(int(t.group(1)), bool(int(t.group(2))), bool(int(t.group(3))))] = figures
     return low_filt, query_filt
 
 

@@ -1,27 +1,19 @@
 """What the compiler made of k_search_side (csrc/fpx_qside.hpp), read from the built code object the way tests/test_kernel_resources.py
 reads k_search_query's: the kernel exists, has no scratch segment and spills no vector register, and its registers and static LDS leave
 room for four workgroups on a CU next to the 39 KB of dynamic LDS it is launched with -- no GPU needed."""
-import glob
-import os
 import re
 
 import pytest
 
-from test_kernel_resources import FIELDS, PKG, _notes      # (the same reader)
+import kernel_notes
 
 
 @pytest.fixture(scope="module")
 def side():
-    lib = os.path.join(PKG, "libfpx.so")
-    search_o = os.path.join(PKG, "build", "fpx_search.o")
-    if not glob.glob(os.path.join(PKG, "build", "*.o")) and not os.path.exists(lib):
-        pytest.skip("nothing built: neither libfpx.so nor build/*.o")
-    notes = _notes(lib if os.path.exists(lib) else search_o)
     found = []
-    for m in re.finditer(r"- \.agpr_count:.*?(?=\n\s+- \.agpr_count:|\namdhsa\.target|\Z)", notes, flags=re.S):
-        blk = m.group(0)
-        if re.search(r"\.name:\s+_ZN3fpx13k_search_sideE", blk):
-            found.append({f: int(re.search(rf"\.{f}:\s+(\d+)", blk).group(1)) for f in FIELDS})
+    for name, figures in kernel_notes.kernels().items():
+        if re.match(r"_ZN3fpx13k_search_sideE", name):
+            found.append(figures)
     assert len(found) == 1, f"k_search_side: {len(found)} kernels of that name in the built code object, one expected"
     return found[0]
 

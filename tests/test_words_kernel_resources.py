@@ -2,31 +2,23 @@
 reads k_search_query's: its eight instantiations (8 / 16 columns x MEM x FILT) exist, none is above 128 vector registers (four workgroups
 per CU next to 39 KB of dynamic LDS each), the unfiltered ones have no scratch segment and spill no vector register, and the static LDS
 leaves room for four workgroups in a CU's 160 KB -- no GPU needed."""
-import glob
-import os
 import re
 
 import pytest
 
-from test_kernel_resources import FIELDS, PKG, _notes      # (the same reader)
+import kernel_notes
 
 WORDS_LDS_BYTES = (8192 + 4) * 4 + (2 << 11) + (8 << 8) + 32 * 8       # SIDE_LDS_BYTES: records, filter, exact table, candidate buffer (SB_CAND = 32)
 
 
 @pytest.fixture(scope="module")
 def words():
-    lib = os.path.join(PKG, "libfpx.so")
-    search_o = os.path.join(PKG, "build", "fpx_search.o")
-    if not glob.glob(os.path.join(PKG, "build", "*.o")) and not os.path.exists(lib):
-        pytest.skip("nothing built: neither libfpx.so nor build/*.o")
-    notes = _notes(lib if os.path.exists(lib) else search_o)
     found = {}
-    for m in re.finditer(r"- \.agpr_count:.*?(?=\n\s+- \.agpr_count:|\namdhsa\.target|\Z)", notes, flags=re.S):
-        blk = m.group(0)
-        t = re.search(r"\.name:\s+_ZN3fpx14k_search_wordsILi(\d+)ELb([01])ELb([01])EEEv", blk)
+    for name, figures in kernel_notes.kernels().items():
+        t = re.match(r"_ZN3fpx14k_search_wordsILi(\d+)ELb([01])ELb([01])EEEv", name)
         if t:
             key = (int(t.group(1)), bool(int(t.group(2))), bool(int(t.group(3))))       # NS, MEM, FILT
-            found[key] = {f: int(re.search(rf"\.{f}:\s+(\d+)", blk).group(1)) for f in FIELDS}
+            found[key] = figures
     return found
 
 
