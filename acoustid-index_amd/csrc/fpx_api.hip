@@ -425,6 +425,7 @@ static const OptInfo OPT_TABLE[OPT_COUNT] = {
     /* OPT_HOT_WG */             {"hot_wg", "FPX_HOT_WG", 0, 0, false},                          // 0 | 1: a query whose records outgrow k_search_query's LDS array hands the batch to the pipeline | is redone in doc classes by k_search_classes (fpx_qsearch.hpp; unfiltered only)
     /* OPT_WORDS_WG */           {"words_wg", "FPX_WORDS_WG", 0, 0, false},                      // 0 | 1 | 2: a snapshot that is ONE group in directory + words form by the pipeline | a query per workgroup (fpx_qwords.hpp) | as 1, a group with superseded docs or masked columns too
     /* OPT_LOW_WG */             {"low_wg", "FPX_LOW_WG", 0, 0, false},                          // 0 | 1 | 2: a batch with queries whose floor is 1 or 2 (the legacy protocol, short fingerprints) goes to the pipeline | stays with k_search_query's path, by k_search_low (fpx_qsearch.hpp; one packed, unfiltered group) | as 1, a group with superseded docs or masked columns too (k_search_low_filt; such a group is on that path under query_wg 2 only)
+    /* OPT_GROUPS_WG */          {"groups_wg", "FPX_GROUPS_WG", 0, 0, false},                    // 0 | 1: a snapshot of SEVERAL packed groups keeps the largest for k_search_query and sends the others through the pipeline | walks up to QS_MAX_GROUPS of them one after the other a query per workgroup (k_search_next, fpx_qsearch.hpp; read per batch, and when a snapshot's two parts are made)
 };
 
 int64_t ctx_opt(const Ctx* c, CtxOpt o)
@@ -1035,8 +1036,12 @@ int fpx_snapshot_create(fpx_ctx* ctx_, fpx_segment* const* segs, uint32_t num_se
     // Under query_wg 2 -- the value in force when the snapshot is made -- part 0 may also be a group with superseded docs or columns outside
     // the snapshot (k_search_query's filtered instantiation).  Its dead sets hold the docs of part 1's segments and of the memory segments
     // as well: they are docs-only members of part 0 (snapshot_build: compute_dead runs over the whole segment list).
+    // Under groups_wg 1 -- the value in force now, as with query_wg -- part 0 holds EVERY packed group that rule accepts, up to QS_MAX_GROUPS
+    // of them, largest first (k_search_next walks the ones behind the first: fpx_qsearch.hpp); with nothing left for part 1 the snapshot
+    // has no parts and is taken whole.
     int g0 = -1;
     uint64_t g0_items = 0;
+    std::vector<std::pair<uint64_t, uint32_t>> packed_ok;       // (items, group): what could be part 0
     const int64_t query_wg = ctx_opt(c, OPT_QUERY_WG);
     if (query_wg != 0 && (sn->n_file != 0 || sn->n_solo != 0 || sn->n_group > 1)) {
         for (uint32_t gi = 0; gi < sn->n_group; ++gi) {
@@ -1047,7 +1052,16 @@ int fpx_snapshot_create(fpx_ctx* ctx_, fpx_segment* const* segs, uint32_t num_se
             uint64_t items = 0;
             for (const Segment* s : sn->segs) if (s->kind == 0 && s->ctx == c && s->home == sn->groups[gi]) items += s->num_items;
             if (g0 < 0 || items > g0_items) { g0 = (int)gi; g0_items = items; }
+            packed_ok.emplace_back(items, gi);
         }
+    }
+    std::vector<uint8_t> in_p0(sn->n_group, 0);
+    uint32_t n_p0 = 0;
+    if (g0 >= 0) {
+        if (ctx_opt(c, OPT_GROUPS_WG) == 1) {
+            std::stable_sort(packed_ok.begin(), packed_ok.end(), [](const auto& x, const auto& y) { return x.first > y.first; });
+            for (size_t i = 0; i < packed_ok.size() && n_p0 < QS_MAX_GROUPS; ++i) { in_p0[packed_ok[i].second] = 1; ++n_p0; }
+        } else { in_p0[g0] = 1; n_p0 = 1; }
     }
     // No packed group for part 0, and option words_wg -- the value in force now -- is set: the largest group in DIRECTORY + WORDS form that
     // is whole here (k_search_words, fpx_qwords.hpp; under words_wg 2 one with superseded docs or columns outside the snapshot too).
@@ -1061,20 +1075,29 @@ int fpx_snapshot_create(fpx_ctx* ctx_, fpx_segment* const* segs, uint32_t num_se
             for (const Segment* s : sn->segs) if (s->kind == 0 && s->ctx == c && s->home == sn->groups[gi]) items += s->num_items;
             if (g0 < 0 || items > g0_items) { g0 = (int)gi; g0_items = items; }
         }
+        if (g0 >= 0) { in_p0[g0] = 1; n_p0 = 1; }
     }
     if (g0 >= 0) {
         bool ok = true;
+        auto home_in_p0 = [&](const Segment* s) {
+            for (uint32_t gi = 0; gi < sn->n_group; ++gi) if (in_p0[gi] && s->home == sn->groups[gi]) return true;
+            return false;
+        };
         std::vector<uint8_t> m0(num_segs, 0), m1(num_segs, 0);
         for (uint32_t i = 0; i < num_segs && ok; ++i) {
             const Segment* s = reinterpret_cast<const Segment*>(segs[i]);
             if (s->kind == 2 || s->ctx != c) continue;
             if (s->kind == 0 && s->own_flags != 0u) ok = false;                    // (a rank's hash window: the sharded protocols' business)
-            else if (s->kind == 1 || s->home == sn->groups[g0]) m0[i] = 1; else m1[i] = 1;
+            else if (s->kind == 1 || home_in_p0(s)) m0[i] = 1; else m1[i] = 1;
         }
         if (ok) {
             Snapshot *p0 = nullptr, *p1 = nullptr;
             if (snapshot_build(c, segs, num_segs, &m0, false, &p0) == FPX_OK && snapshot_build(c, segs, num_segs, &m1, false, &p1) == FPX_OK &&
-                p0->n_group == 1 && p0->n_file == 0 && p0->n_solo == 0 && p0->groups[0] == sn->groups[g0] && p1->n_mem == 0 &&
+                p0->n_group == n_p0 && p0->n_file == 0 && p0->n_solo == 0 && p1->n_mem == 0 &&
+                std::all_of(p0->groups.begin(), p0->groups.end(), [&](const std::shared_ptr<Group>& g) {
+                    for (uint32_t gi = 0; gi < sn->n_group; ++gi) if (in_p0[gi] && g == sn->groups[gi]) return true;
+                    return false;
+                }) &&
                 (p1->n_file != 0 || p1->n_direct != 0) && (p0->n_mem == 0 || p0->mem_items == 0 || p0->d_memtab != nullptr)) {
                 sn->part[0] = p0; sn->part[1] = p1;
             } else {                                                               // (no room, or the forms moved under us: the snapshot works without)

@@ -70,6 +70,7 @@ struct SegDesc {
 };
 
 constexpr uint32_t FUSE_MAX = 16;          // columns of a group
+constexpr uint32_t QS_MAX_GROUPS = 8;      // packed groups of a snapshot walked a query per workgroup, one after the other, at most (option groups_wg: fpx_qsearch.hpp)
 
 // A GROUP of up to 16 direct-addressed segments whose postings are stored together, hash-major and segment-minor, behind one
 // directory (layout: fpx_group.hpp; built by fpx_group.hip).  This is what k_probe_group gets, by value.
@@ -288,7 +289,7 @@ struct Snapshot {
     uint32_t qs_skip = 0;                // batches that stay off the one-workgroup-per-query path (fpx_qsearch.hpp) after a query's records outgrew its LDS array
     std::vector<std::shared_ptr<DirectStore>> solo_stores;       // the arrays d_solo points into
     SegDesc* d_solo = nullptr; uint32_t n_solo = 0;
-    Snapshot* part[2] = {nullptr, nullptr};   // [0]: its ONE packed group (made under words_wg: one in directory + words form) + the memory segments, [1]: its other file segments -- searched apart, tables merged (fpx_snapshot_create); or none
+    Snapshot* part[2] = {nullptr, nullptr};   // [0]: its ONE packed group (made under words_wg: one in directory + words form; under groups_wg: up to QS_MAX_GROUPS packed groups) + the memory segments, [1]: its other file segments -- searched apart, tables merged (fpx_snapshot_create); or none
     uint32_t max_small_blocks = 0;
     MemDesc* d_mem = nullptr; uint32_t n_mem = 0;
     // ... and ONE table of all memory segments' LIVE postings (superseded docs dropped), sorted by hash, behind a 2^20-entry bucket
@@ -382,6 +383,7 @@ enum CtxOpt : int {
     OPT_HOT_WG,
     OPT_WORDS_WG,
     OPT_LOW_WG,
+    OPT_GROUPS_WG,
     OPT_COUNT
 };
 constexpr int64_t OPT_UNSET = -2;

@@ -222,9 +222,15 @@ static_assert(QS_MAX_CLASSES == 32u, "qs_class gives five bits");
 // counted is at or above the floor --: their tail SORTS the record array in place and reads the scores off the runs (under
 // `if constexpr (LOW)`, behind the statistics); a query of the same batch with a floor above 2 takes the tail below as it is.
 constexpr uint32_t QS_LOW_CHUNK = 8;              // (LOW) records a lane sorts in registers (two 16-byte pieces): the network's strides below it cost no barrier
-template <int NS, bool QS, bool MEM, bool FILT, bool CLS, bool LOW = false>
+// ... and a fifth: k_search_next (NEXT true, below; option groups_wg = 1) -- the same walk over a group that is NOT THE FIRST of its
+// batch: a snapshot of several packed groups is walked group by group, a launch each on the batch's stream.  A doc lives in one segment,
+// hence in one group: every launch counts its docs whole and the launches' candidates are disjoint, so they only have to meet in the
+// same slots and the same shared list -- the hand-over CHAINS behind what the launch before left in qcand_n[q], and qstats[q] is
+// added to.  Everything else a launch reports is additive already (atomic adds and maxima into the batch's counters and sets).
+template <int NS, bool QS, bool MEM, bool FILT, bool CLS, bool LOW = false, bool NEXT = false>
 __device__ __forceinline__ void qs_body(const QSearchArgs& a, const GroupArgs& ga)
 {
+    static_assert(!NEXT || (!CLS && !LOW && !MEM), "a later group's walk: no doc classes, no low floors, no memory table (they ride on the first group's launch)");
     static_assert(!(CLS && FILT), "doc classes: the unfiltered walk only");
     static_assert(!LOW || (!CLS && QS_WG == 256u && QS_REC_CAP >= 512u && (QS_REC_CAP & (QS_REC_CAP - 1u)) == 0u),
                   "low floors: no doc classes; the sorted tail's scans are written for 256 lanes and a power-of-two array");
@@ -1087,7 +1093,7 @@ __device__ __forceinline__ void qs_body(const QSearchArgs& a, const GroupArgs& g
     // (the tasks beyond the queue were never read) and would overflow the same queue in every class: that one fails the batch as before.
     const bool q_stats = !CLS || cls == 0u;                  // (CLS: blocks, docs, probes, reads and the histograms in one pass only)
     bool q_redo = false;
-    if constexpr (!FILT && !CLS) {
+    if constexpr (!FILT && !CLS && !NEXT) {
         if (s_over_recs != 0u || s_count > QS_REC_CAP) q_redo = kt->a.redo != nullptr && s_ntask <= TCAP;
     }
     if (tid == 0 && q_redo) {
@@ -1105,7 +1111,8 @@ __device__ __forceinline__ void qs_body(const QSearchArgs& a, const GroupArgs& g
             if (wg_probes) atomicAdd(&st[3], wg_probes);
         }
         if (s_count) atomicAdd(&st[7], (unsigned long long)s_count);                  // the query's hit records ((CLS) this class's: summed over the passes)
-        if constexpr (QS) { if (q_stats) { unsigned long long* const qstats = kt->a.qstats; if (qstats) qstats[q] = wg_blocks | (wg_docs << 32); } }
+        if constexpr (QS && NEXT) { unsigned long long* const qstats = kt->a.qstats; if (qstats) qstats[q] += wg_blocks | (wg_docs << 32); }   // (the query is this workgroup's alone; the launch before is over)
+        else if constexpr (QS) { if (q_stats) { unsigned long long* const qstats = kt->a.qstats; if (qstats) qstats[q] = wg_blocks | (wg_docs << 32); } }
         if (s_over_recs || s_count > QS_REC_CAP) atomicMax(&kt->a.counters[CTR_BINFAIL], 1ull);
     }
     if (tid < HIST_SLOTS - 1u && q_stats && !q_redo) {       // (slot 15: hist_observe's sink)
@@ -1348,6 +1355,44 @@ __device__ __forceinline__ void qs_body(const QSearchArgs& a, const GroupArgs& g
     __syncthreads();
     QS_MARK(4);
     const uint32_t cn = min(s_ccnt, SB_CAND);
+    if constexpr (NEXT) {
+        const qs_kargs_t kh = qs_cold_args();
+        // ---- (NEXT) the CHAINED hand-over.  prev: what the launch before on this stream left for the query -- a kernel boundary lies
+        //      between, a plain load sees it.  (1) prev overflowed: this launch's candidates follow the others into the shared list, the
+        //      mark stays.  (2) nothing of the query went to the shared list here and prev + cn fit the slots: slots [prev, prev + cn).
+        //      (3) the query overflows NOW: its prev slots and the buffer's cn move to the shared list together, one reservation.
+        //      prev indexes nothing unchecked: a workgroup of the first launch that returned at its cancel point wrote no count (a fresh
+        //      allocation may hold anything) -- whatever is neither the mark nor a count of slots is taken for full slots.
+        //      (s_claimed and s_full are the counting passes' and idle here: the carried count and the case, for the workgroup)
+        if (tid == 0) {
+            uint32_t prev = kh->a.qcand_n[q];
+            const bool was = prev == QCAND_OVERFLOWED;
+            prev = was ? 0u : min(prev, QCAND_SLOTS);
+            const bool to_slots = !was && s_cshared == 0u && prev + cn <= QCAND_SLOTS;
+            if (!to_slots) {
+                if (prev + cn != 0u) {
+                    const unsigned long long gi = atomicAdd(&kh->a.counters[CTR_CANDS], (unsigned long long)(prev + cn));
+                    s_cbase_lo = (uint32_t)gi; s_cbase_hi = (uint32_t)(gi >> 32);
+                }
+                if (!was) kh->a.qcand_n[q] = QCAND_OVERFLOWED;
+            } else kh->a.qcand_n[q] = prev + cn;
+            s_claimed = prev; s_full = to_slots ? 1u : 0u;
+        }
+        __syncthreads();
+        const uint32_t prev = s_claimed;
+        const bool to_slots = s_full != 0u;
+        const uint64_t base = ((uint64_t)s_cbase_hi << 32) | s_cbase_lo;
+        if (tid < cn) {
+            const uint64_t key = cbuf[tid];
+            if (to_slots) kh->a.qcand[(size_t)q * QCAND_SLOTS + prev + tid] = key;      // (prev + cn <= QCAND_SLOTS)
+            else if (base + tid < kh->a.cand_cap) kh->a.cands[base + tid] = key;
+        }
+        static_assert(SB_CAND + QCAND_SLOTS <= QS_WG, "the carried slots move by lanes of their own");
+        if (const uint32_t t = tid - SB_CAND; !to_slots && t < prev) {                   // (prev <= QCAND_SLOTS; tid < SB_CAND wraps to a large t)
+            const uint64_t gi = base + cn + t;
+            if (gi < kh->a.cand_cap) kh->a.cands[gi] = kh->a.qcand[(size_t)q * QCAND_SLOTS + t];
+        }
+    } else {
     const bool shared = s_cshared != 0u || cn > QCAND_SLOTS;
     const qs_kargs_t kh = qs_cold_args();
     if (tid == 0) {
@@ -1365,6 +1410,7 @@ __device__ __forceinline__ void qs_body(const QSearchArgs& a, const GroupArgs& g
             const uint64_t gi = (((uint64_t)s_cbase_hi << 32) | s_cbase_lo) + tid;
             if (gi < kh->a.cand_cap) kh->a.cands[gi] = key;
         }
+    }
     }
     QS_MARK(5);
     if constexpr (CLS) {                                // the workgroup's next entry of the redo list
@@ -1427,6 +1473,15 @@ template <int NS, bool QS, bool MEM>
 __global__ __launch_bounds__(QS_WG) FPX_QS_OCC void k_search_low_filt(QSearchArgs a, GroupArgs ga)
 {
     qs_body<NS, QS, MEM, true, false, true>(a, ga);
+}
+
+// k_search_next (option groups_wg = 1): k_search_query's body over a group that is not the first of its batch's (qs_body: `NEXT`) -- the
+// chained hand-over, qstats added to.  No redo list (a.redo is null), no low floors, no memory table: the memory segments ride on the
+// first group's launch, an ordinary k_search_query.  The same two by-value parameters.
+template <int NS, bool QS, bool FILT>
+__global__ __launch_bounds__(QS_WG) FPX_QS_OCC void k_search_next(QSearchArgs a, GroupArgs ga)
+{
+    qs_body<NS, QS, false, FILT, false, false, true>(a, ga);
 }
 
 // zeroes what a batch of k_search_query adds to: the batch's counters and the statistics sets (one launch instead of two memsets)

@@ -13,7 +13,8 @@
 //      (run_query_wg; run_side_wg for the file segments next to the group; run_words_wg -- option words_wg, k_search_words in
 //      fpx_qwords.hpp -- for a snapshot that is one group in directory + words form).  A batch with queries whose floor is 1 or 2 is B's,
 //      or -- option low_wg: 1 an unfiltered packed group, 2 a filtered one too -- run_query_wg's with k_search_low (k_search_low_filt) in
-//      k_search_query's place.
+//      k_search_query's place.  A snapshot of SEVERAL packed groups is B's, or -- option groups_wg = 1 -- run_query_wg's: the groups walked
+//      one after the other, k_search_query over the first, k_search_next over the others, one k_finish.
 //   B. everything else, the pipeline over all the batch's hashes (make_keys, launch_probes; run_device_sized, run_single or run_general):
 //      1. k_make_keys*     (hash, q) keys, packed hash << QB | q; ordered by hash bucket (fpx_keyorder.hpp / fpx_sort.hip) or per query in LDS:
 //                          duplicates become adjacent (dedupSorted) and neighbouring probes walk neighbouring lines
@@ -707,11 +708,29 @@ static bool low_floors_ok(const Ctx* ctx, bool filtered)
     const int64_t low_wg = ctx_opt(ctx, OPT_LOW_WG);
     return low_wg == 2 || (low_wg == 1 && !filtered);
 }
+// Option groups_wg 1: a snapshot of 2 .. QS_MAX_GROUPS packed groups too -- every one whole-hash-space, nothing else next to them --, walked
+// one after the other (run_query_wg: k_search_next).  *filt: ANY of them is filtered (under query_wg 2 only, as for one); no query with a
+// floor of 1 or 2, whatever low_wg says.  One group: exactly as before.
+static bool several_groups_ok(const Snapshot* snap)
+{
+    if (snap->n_group < 2u || snap->n_group > QS_MAX_GROUPS || ctx_opt(snap->ctx, OPT_GROUPS_WG) != 1) return false;
+    for (uint32_t i = 0; i < snap->n_group; ++i)
+        if (!snap->groups[i]->packed || snap->h_group[i].win_lo != 0u || snap->h_group[i].win_hi != 0xFFFFFFFFu) return false;
+    return true;
+}
 static bool takes_query_wg(const Snapshot* snap, const uint64_t* offsets, const fpx_opts* opts, uint32_t B, bool* filt, bool* low)
 {
     const int64_t query_wg = ctx_opt(snap->ctx, OPT_QUERY_WG);
-    if (!(snap->n_file == 0 && snap->n_solo == 0 && snap->n_group == 1 && snap->n_direct != 0 &&
-          (snap->n_mem == 0 || snap->mem_items == 0 || snap->d_memtab != nullptr) && snap->groups[0]->packed && query_wg != 0)) return false;
+    if (!(snap->n_file == 0 && snap->n_solo == 0 && snap->n_group >= 1 && snap->n_direct != 0 &&
+          (snap->n_mem == 0 || snap->mem_items == 0 || snap->d_memtab != nullptr) && query_wg != 0)) return false;
+    if (snap->n_group != 1) {
+        if (!several_groups_ok(snap)) return false;
+        *filt = false;
+        for (uint32_t i = 0; i < snap->n_group; ++i) *filt = *filt || group_filtered(snap->h_group[i]);
+        *low = false;
+        return (!*filt || query_wg == 2) && queries_fit_wg(offsets, opts, B);
+    }
+    if (!snap->groups[0]->packed) return false;
     *filt = group_filtered(snap->h_group[0]);
     return (!*filt || query_wg == 2) && queries_fit_wg(offsets, opts, B, low_floors_ok(snap->ctx, *filt), low);
 }
@@ -779,6 +798,16 @@ static void launch_search_low_filt(bool ns8, bool qs, bool mem, dim3 grid, hipSt
     else { if (qs) FPX_LF_MEM(16, true); else FPX_LF_MEM(16, false); }
 #undef FPX_LF_MEM
 #undef FPX_LF
+}
+// ... and k_search_next's (a group that is not the first of its batch's: option groups_wg = 1)
+static void launch_search_next(bool ns8, bool qs, bool filt, dim3 grid, hipStream_t st, const QSearchArgs& qa, const GroupArgs& g)
+{
+#define FPX_LN(NS, QSV, FILT) hipLaunchKernelGGL((k_search_next<NS, QSV, FILT>), grid, dim3(QS_WG), QS_LDS_BYTES, st, qa, g)
+#define FPX_LN_FILT(NS, QSV) do { if (filt) FPX_LN(NS, QSV, true); else FPX_LN(NS, QSV, false); } while (0)
+    if (ns8) { if (qs) FPX_LN_FILT(8, true); else FPX_LN_FILT(8, false); }
+    else { if (qs) FPX_LN_FILT(16, true); else FPX_LN_FILT(16, false); }
+#undef FPX_LN_FILT
+#undef FPX_LN
 }
 // a query-per-workgroup path opens: the queries' candidate slots (`extra_words` of the caller's behind them), the counters and statistics
 // sets zeroed, the probe's first event -- and the arguments every such kernel takes, from the batch (Args: QFrameArgs | QSearchArgs,
@@ -859,12 +888,18 @@ static int redo_hot_queries(Batch& b, QSearchArgs qa, const GroupArgs& gargs, bo
 // low: the batch has queries with a floor of 1 or 2 (option low_wg let it in; with filt under low_wg 2 only) -- k_search_low, or
 // k_search_low_filt on a filtered group; neither has a redo list.
 // Every other batch is k_search_query's exactly as before, whatever that option says.
+// SEVERAL GROUPS (option groups_wg = 1; takes_query_wg): per upload piece the groups are walked one after the other on the batch's stream --
+// k_search_query over group 0 (with the memory segments' table), k_search_next over groups 1.., which chain their candidates behind the
+// launch before (fpx_qsearch.hpp).  The batch is opened once and closed once, one k_finish; a hand-back from any launch is the batch's.
+// No redo list and no low floors there; filt: ANY group is filtered -- which instantiation a launch is is its own group's business.
+static_assert(QS_MAX_GROUPS * Workspace::UP_CHUNKS <= DEF_COUNT_STRIDE, "the launches' next_q words -- one per (upload piece, group) -- are the first deferred-list count's line, which k_qs_zero clears");
 static int run_query_wg(Batch& b, bool filt, bool low)
 {
     Snapshot* snap = b.snap; Workspace* ws = b.ws; hipStream_t st = b.st; const uint32_t B = b.B; int rc;
+    const uint32_t ngroups = snap->n_group;
     const bool ns8 = snap->groups[0]->ns == 8u;
     // (option hot_wg = 1, unfiltered: the batch's redo list -- B entries, behind the slots and their counts)
-    const bool hot_wg = !filt && !low && ctx_opt(snap->ctx, OPT_HOT_WG) == 1;
+    const bool hot_wg = !filt && !low && ngroups == 1u && ctx_opt(snap->ctx, OPT_HOT_WG) == 1;
     if (low) {
         // (a query with a low floor hands over up to max_results candidates -- the legacy protocol's 500 --, all of them through the shared
         // list once they are more than its slots: the list is sized for that, not for the first guess of 64 per query)
@@ -891,6 +926,7 @@ static int run_query_wg(Batch& b, bool filt, bool low)
     // as many workgroups as the chip holds at once (LDS: QS_WGS_PER_CU per CU); each takes every gridDim.x-th query
     const int cus = device_cus(snap->ctx);
     const uint32_t up_chunks = b.up_chunks;
+    uint32_t next_launches = 0;
     for (uint32_t c = 0; c < std::max(1u, up_chunks); ++c) {
         qa.q_begin = up_chunks ? b.up_q[c] : 0u; qa.q_end = up_chunks ? b.up_q[c + 1] : B;
         if (qa.q_end == qa.q_begin) { if (up_chunks && c + 1u < up_chunks && (rc = upload_piece(b, c + 1u))) return rc; continue; }
@@ -900,7 +936,18 @@ static int run_query_wg(Batch& b, bool filt, bool low)
         qa.stagger = alone ? QS_STAGGER : 0u;
         if (up_chunks) FPX_HIP(hipStreamWaitEvent(st, ws->ev_chunk[c], 0));           // (the piece's hashes have arrived; the next piece is on its way)
         const dim3 grid(std::min<uint32_t>(qa.q_end - qa.q_begin, (uint32_t)cus * QS_WGS_PER_CU));
-        if (low && filt) launch_search_low_filt(ns8, b.want_q, qa.mem_tab != nullptr, grid, st, qa, gargs);
+        if (ngroups > 1u) {
+            // (the piece's queries over group 0, then over every other group: a launch's queue of queries is a word of its own)
+            launch_search_query(ns8, b.want_q, qa.mem_tab != nullptr, group_filtered(snap->h_group[0]), grid, st, qa, gargs);
+            QSearchArgs qn = qa;
+            qn.mem_tab = nullptr; qn.mem_bucket = nullptr; qn.mem_bits = nullptr;
+            for (uint32_t gi = 1; gi < ngroups; ++gi) {
+                qn.next_q = qa.next_q ? ws->d_def_count + (size_t)gi * Workspace::UP_CHUNKS + c : nullptr;
+                launch_search_next(snap->groups[gi]->ns == 8u, b.want_q, group_filtered(snap->h_group[gi]), grid, st, qn, GroupArgs{snap->h_group[gi], snap->d_direct});
+                ++next_launches;
+            }
+        }
+        else if (low && filt) launch_search_low_filt(ns8, b.want_q, qa.mem_tab != nullptr, grid, st, qa, gargs);
         else if (low) launch_search_low(ns8, b.want_q, qa.mem_tab != nullptr, grid, st, qa, gargs);
         else launch_search_query(ns8, b.want_q, qa.mem_tab != nullptr, filt, grid, st, qa, gargs);
         if (up_chunks && c + 1u < up_chunks && (rc = upload_piece(b, c + 1u))) return rc;       // (the next piece crosses PCIe under this kernel)
@@ -926,7 +973,9 @@ static int run_query_wg(Batch& b, bool filt, bool low)
         Cf = ws->h_counters[CTR_CANDS];
         if ((rc = finish_crowded(b, qa.sb, cs, to, Cf))) return rc;
     }
-    return finish_wg_path(b, to, Cf, 4u | 64u | (filt ? 256u : 0u) | (R != 0 ? 1024u : 0u) | (low ? 4096u : 0u));
+    if ((rc = finish_wg_path(b, to, Cf, 4u | 64u | (filt ? 256u : 0u) | (R != 0 ? 1024u : 0u) | (low ? 4096u : 0u) | (ngroups > 1u ? 8192u : 0u)))) return rc;
+    if (b.stats) b.stats->probe_launches += next_launches;
+    return FPX_OK;
 }
 
 // ... and the file segments next to the group, by k_search_side
@@ -1738,9 +1787,14 @@ static bool parts_take(const Snapshot* snap, const uint64_t* offsets, const fpx_
     // (a part 0 in directory + words form -- made under words_wg -- while THAT option allows it)
     const int64_t query_wg = ctx_opt(snap->ctx, snap->part[0]->groups[0]->packed ? OPT_QUERY_WG : OPT_WORDS_WG);
     if (query_wg == 0) return false;
-    const bool filtered = group_filtered(snap->part[0]->h_group[0]), packed = snap->part[0]->groups[0]->packed;
+    const Snapshot* p0 = snap->part[0];
+    bool filtered = false;                                       // (ANY group of part 0)
+    for (uint32_t i = 0; i < p0->n_group; ++i) filtered = filtered || group_filtered(p0->h_group[i]);
+    const bool packed = p0->groups[0]->packed;
     if (query_wg != 2 && filtered) return false;
     if (bits_for(B) > 24u || offsets[B] == offsets[0]) return false;
+    // (a part 0 of several groups -- made under groups_wg -- while that option allows it, and for batches without low floors)
+    if (p0->n_group > 1u) return several_groups_ok(p0) && queries_fit_wg(offsets, opts, B);
     // (floors of 1 and 2: takes_query_wg's rule -- option low_wg, a packed part 0; a filtered one under 2 only)
     return queries_fit_wg(offsets, opts, B, packed && low_floors_ok(snap->ctx, filtered));
 }
