@@ -129,6 +129,7 @@ __device__ __forceinline__ qs_kargs_t qs_cold_args()
 }
 
 #define FPX_QS_OCC __attribute__((amdgpu_waves_per_eu(FPX_QS_WAVES)))
+#define FPX_LDS __attribute__((address_space(3)))
 typedef uint32_t u32x3_t __attribute__((ext_vector_type(3)));
 __device__ __forceinline__ uint3 gload_u3(const uint32_t* p)            // the first three words of a line (16-byte aligned)
 {
@@ -494,10 +495,18 @@ __device__ __forceinline__ void qs_body(const QSearchArgs& a, const GroupArgs& g
         constexpr uint32_t N = sizeof(d) / sizeof(uint32_t);
         if (cnt != 0u && pos + cnt > QS_REC_CAP) { s_over_recs = 1u; km = 0u; cnt = 0u; }      // (more records than the array takes: the batch goes the long way)
         const uint32_t first = cnt != 0u ? pos : QS_REC_CAP, sink = QS_REC_CAP - first;
+        // (the lane's base in LDS -- the array's address and `first` -- is made ONCE, as a 32-bit LDS address in a vector register: a
+        // slot's address is then one shift-and-add of it (v_lshl_add_u32) where the array's scalar base, the shifted index and the
+        // shifted `first` cost a shift and a three-operand add per slot.  (CLS keeps the generic form: with the memory table's
+        // registers its sixteen-column rounds are at the 128 a lane has, and the base held across the stores spilled one)
+        auto last_of = [&](uint32_t j) -> uint32_t { return (uint32_t)__popc(km & ((2u << j) - 1u)) - 1u; };      // the last doc up to slot j among the lane's (none: 0xFFFFFFFF)
+        if constexpr (CLS) {
 #pragma unroll
-        for (uint32_t j = N; j-- != 0u;) {
-            const uint32_t last = (uint32_t)__popc(km & ((2u << j) - 1u)) - 1u;      // the last doc up to slot j among the lane's (none: 0xFFFFFFFF)
-            recs[first + min(last, sink)] = d[j];
+            for (uint32_t j = N; j-- != 0u;) recs[first + min(last_of(j), sink)] = d[j];
+        } else {
+            FPX_LDS uint32_t* const base = (FPX_LDS uint32_t*)(recs + first);
+#pragma unroll
+            for (uint32_t j = N; j-- != 0u;) base[min(last_of(j), sink)] = d[j];
         }
     };
     auto emit = [&](uint32_t km, const auto& d) {
@@ -1077,13 +1086,22 @@ __device__ __forceinline__ void qs_body(const QSearchArgs& a, const GroupArgs& g
     const uint32_t nrec = min(s_count, QS_REC_CAP);
     // ---- SearchResults.incr (src/common.zig:121-129), first the filter: every record into its doc's cell
     // (four records per lane and turn, read as one 16-byte piece: the loop is a chain of LDS latencies -- a record, then its cell)
+    // (a lane's four are all records in every turn but the query's last: only that one tests record by record)
     for (uint32_t i = tid * 4u; i < nrec; i += QS_WG * 4u) {
         const uint4 r4 = *reinterpret_cast<const uint4*>(recs + i);             // (the array ends with four spare words)
         const uint32_t r[4] = {r4.x, r4.y, r4.z, r4.w};
+        if (i + 3u < nrec) {
 #pragma unroll
-        for (uint32_t u = 0; u < 4u; ++u) {
-            const uint32_t c = qs_cell(r[u]);
-            if (i + u < nrec) atomicAdd(&filter[c >> 1], 1u << (16u * (c & 1u)));
+            for (uint32_t u = 0; u < 4u; ++u) {
+                const uint32_t c = qs_cell(r[u]);
+                atomicAdd(&filter[c >> 1], 1u << (16u * (c & 1u)));
+            }
+        } else {
+#pragma unroll
+            for (uint32_t u = 0; u < 4u; ++u) {
+                const uint32_t c = qs_cell(r[u]);
+                if (i + u < nrec) atomicAdd(&filter[c >> 1], 1u << (16u * (c & 1u)));
+            }
         }
     }
     const qs_kargs_t kt = qs_cold_args();               // (the tail's arguments: read here, once per query)
@@ -1284,47 +1302,65 @@ __device__ __forceinline__ void qs_body(const QSearchArgs& a, const GroupArgs& g
       }
     }
     if (!low_q && s_over_recs == 0u && !q_redo && nrec != 0u && nrec >= floor_q) {
+        if (tid == 0) { s_claimed = 0u; s_full = 0u; }
+        __syncthreads();                                // (the filter's counts are complete behind this barrier)
+        // (a) the SWEEP: four records per lane and turn and their four cells, nothing else -- a record whose cell reaches the floor is a
+        // bit of the lane's mask, bit 4 turn + u for record turn * 4 QS_WG + 4 tid + u.  Made once per query (and class): the filter does
+        // not change between the passes.  Only the query's last turn tests record by record.
+        static_assert((QS_REC_CAP + QS_WG * 4u - 1u) / (QS_WG * 4u) <= 8u, "a lane's turns over a query's records: at most 8, four bits of its mask each");
+        uint32_t surv = 0u;
+        uint32_t t4 = tid * 4u;
+        asm volatile("" : "+v"(t4));
+        for (uint32_t i4 = t4, sh = 0u; i4 < nrec; i4 += QS_WG * 4u, sh += 4u) {
+            const uint4 r4 = *reinterpret_cast<const uint4*>(recs + i4);
+            const uint32_t r[4] = {r4.x, r4.y, r4.z, r4.w};
+            uint32_t cnt4[4];
+#pragma unroll
+            for (uint32_t u = 0; u < 4u; ++u) { const uint32_t c = qs_cell(r[u]); cnt4[u] = (filter[c >> 1] >> (16u * (c & 1u))) & 0xFFFFu; }
+            uint32_t m4 = 0u;
+            if (i4 + 3u < nrec) {
+#pragma unroll
+                for (uint32_t u = 0; u < 4u; ++u) m4 |= (cnt4[u] >= floor_q ? 1u : 0u) << u;
+            } else {
+#pragma unroll
+                for (uint32_t u = 0; u < 4u; ++u) m4 |= (i4 + u < nrec && cnt4[u] >= floor_q ? 1u : 0u) << u;
+            }
+            surv |= m4 << sh;
+        }
         uint32_t passes = 1u;
         for (uint32_t pass = 0; pass < passes; ++pass) {
-            if (pass != 0u) {
-                __syncthreads();
-                for (uint32_t s = tid; s < T; s += QS_WG) table[s] = 0ull;
-            }
-            if (tid == 0) { s_claimed = 0u; s_full = 0u; }
-            __syncthreads();                            // (the first pass: the filter's counts are complete behind this barrier)
-            for (uint32_t i4 = tid * 4u; i4 < nrec; i4 += QS_WG * 4u) {
-              const uint4 r4 = *reinterpret_cast<const uint4*>(recs + i4);
-              const uint32_t r[4] = {r4.x, r4.y, r4.z, r4.w};
-              uint32_t cnt4[4];
-#pragma unroll
-              for (uint32_t u = 0; u < 4u; ++u) { const uint32_t c = qs_cell(r[u]); cnt4[u] = (filter[c >> 1] >> (16u * (c & 1u))) & 0xFFFFu; }
-#pragma unroll
-              for (uint32_t u = 0; u < 4u; ++u) {
-                const uint32_t doc = r[u];
-                if (i4 + u >= nrec || cnt4[u] < floor_q) continue;
-                const uint32_t h2 = mix32(doc);
-                if (passes > 1u && (h2 >> 16) % passes != pass) continue;
-                const unsigned long long keyhi = (unsigned long long)doc << 32;
-                uint32_t s = h2 & TMASK;
-                for (uint32_t tries = 0;; ++tries) {
-                    if (tries == T) { s_full = 1u; break; }
-                    unsigned long long cur = table[s];
-                    if (cur == 0ull) {
-                        const unsigned long long prev = atomicCAS(&table[s], 0ull, keyhi | 1ull);
-                        if (prev == 0ull) { atomicAdd(&s_claimed, 1u); break; }
-                        cur = prev;
+            // (b) the DRAIN: a lane with a bit left takes its lowest one, reads that record back and counts it in the table; the wave
+            // makes as many trips as its fullest lane has bits.  Every pass drains a copy of the mask.
+            for (uint32_t left = surv; __ballot((int)(left != 0u)) != 0ull;) {
+                if (left != 0u) {
+                    const uint32_t bit = (uint32_t)__builtin_ctz(left);
+                    left &= left - 1u;
+                    const uint32_t doc = recs[(bit >> 2) * (QS_WG * 4u) + t4 + (bit & 3u)];
+                    const uint32_t h2 = mix32(doc);
+                    if (passes == 1u || (h2 >> 16) % passes == pass) {
+                        const unsigned long long keyhi = (unsigned long long)doc << 32;
+                        uint32_t s = h2 & TMASK;
+                        for (uint32_t tries = 0;; ++tries) {
+                            if (tries == T) { s_full = 1u; break; }
+                            unsigned long long cur = table[s];
+                            if (cur == 0ull) {
+                                const unsigned long long prev = atomicCAS(&table[s], 0ull, keyhi | 1ull);
+                                if (prev == 0ull) { atomicAdd(&s_claimed, 1u); break; }
+                                cur = prev;
+                            }
+                            if ((cur >> 32) == (keyhi >> 32)) { atomicAdd(&table[s], 1ull); break; }
+                            s = (s + 1u) & TMASK;
+                        }
                     }
-                    if ((cur >> 32) == (keyhi >> 32)) { atomicAdd(&table[s], 1ull); break; }
-                    s = (s + 1u) & TMASK;
                 }
-              }
             }
             __syncthreads();
             if (pass == 0u && (s_claimed > T * 3u / 4u || s_full != 0u) && passes < 64u) {
-                const uint32_t np = passes * 2u;
-                __syncthreads();
+                __syncthreads();                        // (everybody has read the flags)
                 for (uint32_t s = tid; s < T; s += QS_WG) table[s] = 0ull;
-                passes = np; pass = 0xFFFFFFFFu;           // (++pass: 0 again; nothing has been emitted yet)
+                if (tid == 0) { s_claimed = 0u; s_full = 0u; }
+                passes *= 2u; pass = 0xFFFFFFFFu;       // (++pass: 0 again; nothing has been emitted yet)
+                __syncthreads();
                 continue;
             }
             const qs_kargs_t kc = qs_cold_args();
@@ -1347,6 +1383,12 @@ __device__ __forceinline__ void qs_body(const QSearchArgs& a, const GroupArgs& g
                     if (gi < kc->a.cand_cap) kc->a.cands[gi] = key;
                     s_cshared = 1u;
                 }
+            }
+            if (pass + 1u < passes) {                   // (the next pass's table and flags)
+                __syncthreads();
+                for (uint32_t s = tid; s < T; s += QS_WG) table[s] = 0ull;
+                if (tid == 0) { s_claimed = 0u; s_full = 0u; }
+                __syncthreads();
             }
         }
     }
