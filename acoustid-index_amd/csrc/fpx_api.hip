@@ -425,7 +425,7 @@ static const OptInfo OPT_TABLE[OPT_COUNT] = {
     /* OPT_HOT_WG */             {"hot_wg", "FPX_HOT_WG", 0, 0, false},                          // 0 | 1: a query whose records outgrow k_search_query's LDS array hands the batch to the pipeline | is redone in doc classes by k_search_classes (fpx_qsearch.hpp; unfiltered only)
     /* OPT_WORDS_WG */           {"words_wg", "FPX_WORDS_WG", 0, 0, false},                      // 0 | 1 | 2: a snapshot that is ONE group in directory + words form by the pipeline | a query per workgroup (fpx_qwords.hpp) | as 1, a group with superseded docs or masked columns too
     /* OPT_LOW_WG */             {"low_wg", "FPX_LOW_WG", 0, 0, false},                          // 0 | 1 | 2: a batch with queries whose floor is 1 or 2 (the legacy protocol, short fingerprints) goes to the pipeline | stays with k_search_query's path, by k_search_low (fpx_qsearch.hpp; one packed, unfiltered group) | as 1, a group with superseded docs or masked columns too (k_search_low_filt; such a group is on that path under query_wg 2 only)
-    /* OPT_GROUPS_WG */          {"groups_wg", "FPX_GROUPS_WG", 0, 0, false},                    // 0 | 1: a snapshot of SEVERAL packed groups keeps the largest for k_search_query and sends the others through the pipeline | walks up to QS_MAX_GROUPS of them one after the other a query per workgroup (k_search_next, fpx_qsearch.hpp; read per batch, and when a snapshot's two parts are made)
+    /* OPT_GROUPS_WG */          {"groups_wg", "FPX_GROUPS_WG", 0, 0, false},                    // 0 | 1 | 2: a snapshot of SEVERAL packed groups keeps the largest for k_search_query and sends the others through the pipeline | walks up to QS_MAX_GROUPS of them one after the other a query per workgroup (k_search_next, fpx_qsearch.hpp; read per batch, and when a snapshot's two parts are made) | as 1, a batch with queries whose floor is 1 or 2 too where low_wg allows it (1: no group filtered, 2: any; k_search_low / k_search_low_filt over the first group, k_search_low_next over the others)
 };
 
 int64_t ctx_opt(const Ctx* c, CtxOpt o)
@@ -1036,7 +1036,7 @@ int fpx_snapshot_create(fpx_ctx* ctx_, fpx_segment* const* segs, uint32_t num_se
     // Under query_wg 2 -- the value in force when the snapshot is made -- part 0 may also be a group with superseded docs or columns outside
     // the snapshot (k_search_query's filtered instantiation).  Its dead sets hold the docs of part 1's segments and of the memory segments
     // as well: they are docs-only members of part 0 (snapshot_build: compute_dead runs over the whole segment list).
-    // Under groups_wg 1 -- the value in force now, as with query_wg -- part 0 holds EVERY packed group that rule accepts, up to QS_MAX_GROUPS
+    // Under groups_wg 1 or 2 -- the value in force now, as with query_wg -- part 0 holds EVERY packed group that rule accepts, up to QS_MAX_GROUPS
     // of them, largest first (k_search_next walks the ones behind the first: fpx_qsearch.hpp); with nothing left for part 1 the snapshot
     // has no parts and is taken whole.
     int g0 = -1;
@@ -1058,7 +1058,7 @@ int fpx_snapshot_create(fpx_ctx* ctx_, fpx_segment* const* segs, uint32_t num_se
     std::vector<uint8_t> in_p0(sn->n_group, 0);
     uint32_t n_p0 = 0;
     if (g0 >= 0) {
-        if (ctx_opt(c, OPT_GROUPS_WG) == 1) {
+        if (const int64_t groups_wg = ctx_opt(c, OPT_GROUPS_WG); groups_wg == 1 || groups_wg == 2) {
             std::stable_sort(packed_ok.begin(), packed_ok.end(), [](const auto& x, const auto& y) { return x.first > y.first; });
             for (size_t i = 0; i < packed_ok.size() && n_p0 < QS_MAX_GROUPS; ++i) { in_p0[packed_ok[i].second] = 1; ++n_p0; }
         } else { in_p0[g0] = 1; n_p0 = 1; }

@@ -38,6 +38,9 @@
 // such a query's records are sorted in LDS and its scores read off the runs, only the top max_results leave.  A launch of k_search_low
 // carries no redo list: hot_wg is ignored for such a batch.  Option low_wg = 2: as 1, and under query_wg = 2 a FILTERED group too, by
 // k_search_low_filt -- the filtered walk below leaves live docs only in the record array, which is all the sorted tail asks for.
+// Option groups_wg = 1: a snapshot of several packed groups is walked group by group, k_search_next over the groups behind the first;
+// groups_wg = 2: as 1, and with low_wg a batch with floors of 1 or 2 too -- k_search_low (k_search_low_filt) over the first group,
+// k_search_low_next over the others.
 // FILT (option query_wg = 2): the same for a group with superseded docs and/or columns outside the snapshot (a live index between a
 // merge and its regroup) -- every word knows its column, as in k_probe_pgroup's per-column walk: a column outside `active` gives no
 // record and no statistic, a doc of a column with a dead set is dropped after it was counted (CTR_DOCS counts before supersession).
@@ -228,10 +231,13 @@ constexpr uint32_t QS_LOW_CHUNK = 8;              // (LOW) records a lane sorts 
 // hence in one group: every launch counts its docs whole and the launches' candidates are disjoint, so they only have to meet in the
 // same slots and the same shared list -- the hand-over CHAINS behind what the launch before left in qcand_n[q], and qstats[q] is
 // added to.  Everything else a launch reports is additive already (atomic adds and maxima into the batch's counters and sets).
+// ... and a sixth: k_search_low_next (LOW and NEXT true, below; option groups_wg = 2 with low_wg) -- a later group's walk for a batch
+// with floors of 1 or 2: the sorted tail's candidates -- each group's top max_results under its own raised floor, a superset of what
+// k_finish keeps of the group -- go through the same buffer, flags and shared list into the chained hand-over.
 template <int NS, bool QS, bool MEM, bool FILT, bool CLS, bool LOW = false, bool NEXT = false>
 __device__ __forceinline__ void qs_body(const QSearchArgs& a, const GroupArgs& ga)
 {
-    static_assert(!NEXT || (!CLS && !LOW && !MEM), "a later group's walk: no doc classes, no low floors, no memory table (they ride on the first group's launch)");
+    static_assert(!NEXT || (!CLS && !MEM), "a later group's walk: no doc classes, no memory table (they ride on the first group's launch)");
     static_assert(!(CLS && FILT), "doc classes: the unfiltered walk only");
     static_assert(!LOW || (!CLS && QS_WG == 256u && QS_REC_CAP >= 512u && (QS_REC_CAP & (QS_REC_CAP - 1u)) == 0u),
                   "low floors: no doc classes; the sorted tail's scans are written for 256 lanes and a power-of-two array");
@@ -1524,6 +1530,21 @@ template <int NS, bool QS, bool FILT>
 __global__ __launch_bounds__(QS_WG) FPX_QS_OCC void k_search_next(QSearchArgs a, GroupArgs ga)
 {
     qs_body<NS, QS, false, FILT, false, false, true>(a, ga);
+}
+
+// k_search_low_next (option groups_wg = 2 with low_wg): the same over a later group for a batch that HAS queries with a floor of 1 or 2
+// (qs_body: `LOW` and `NEXT`) -- those take the sorted tail, the batch's other queries the usual one, and both end in the chained
+// hand-over.  The first group's launch is k_search_low or k_search_low_filt.  What the composition rests on: the records become absolute
+// ids with the gmin of THIS launch's group (the kernel's own GroupArgs); the sorted tail leaves its candidates where the usual one does
+// -- cbuf, s_ccnt, s_cshared and the shared list --, its scratch is the filter's area, and it never touches s_claimed / s_full, which
+// the chained hand-over takes behind the tail's last barrier; a query without a record here (or with fewer than its floor) skips both
+// tails with s_ccnt = 0, and the hand-over then leaves the earlier launches' slots, count and mark as they are; qstats[q] is added to.
+// The floor a launch raises by its own group's best score is a lower bound of the one k_finish applies, and the union of every group's
+// top max_results in (score descending, id ascending) order holds the snapshot's.  FILT as in k_search_low_filt; no memory table.
+template <int NS, bool QS, bool FILT>
+__global__ __launch_bounds__(QS_WG) FPX_QS_OCC void k_search_low_next(QSearchArgs a, GroupArgs ga)
+{
+    qs_body<NS, QS, false, FILT, false, true, true>(a, ga);
 }
 
 // zeroes what a batch of k_search_query adds to: the batch's counters and the statistics sets (one launch instead of two memsets)

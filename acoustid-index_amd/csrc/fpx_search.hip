@@ -14,7 +14,9 @@
 //      fpx_qwords.hpp -- for a snapshot that is one group in directory + words form).  A batch with queries whose floor is 1 or 2 is B's,
 //      or -- option low_wg: 1 an unfiltered packed group, 2 a filtered one too -- run_query_wg's with k_search_low (k_search_low_filt) in
 //      k_search_query's place.  A snapshot of SEVERAL packed groups is B's, or -- option groups_wg = 1 -- run_query_wg's: the groups walked
-//      one after the other, k_search_query over the first, k_search_next over the others, one k_finish.
+//      one after the other, k_search_query over the first, k_search_next over the others, one k_finish.  Both together -- several groups
+//      and a low floor in the batch -- are B's, or, option groups_wg = 2 with low_wg, run_query_wg's: k_search_low (k_search_low_filt)
+//      over the first group, k_search_low_next over the others.
 //   B. everything else, the pipeline over all the batch's hashes (make_keys, launch_probes; run_device_sized, run_single or run_general):
 //      1. k_make_keys*     (hash, q) keys, packed hash << QB | q; ordered by hash bucket (fpx_keyorder.hpp / fpx_sort.hip) or per query in LDS:
 //                          duplicates become adjacent (dedupSorted) and neighbouring probes walk neighbouring lines
@@ -711,12 +713,19 @@ static bool low_floors_ok(const Ctx* ctx, bool filtered)
 // Option groups_wg 1: a snapshot of 2 .. QS_MAX_GROUPS packed groups too -- every one whole-hash-space, nothing else next to them --, walked
 // one after the other (run_query_wg: k_search_next).  *filt: ANY of them is filtered (under query_wg 2 only, as for one); no query with a
 // floor of 1 or 2, whatever low_wg says.  One group: exactly as before.
+// Option groups_wg 2: as 1, and a batch with floors of 1 or 2 too where low_wg allows it (several_groups_low_ok: low_wg 1 when no group
+// is filtered, 2 also when any is) -- k_search_low / k_search_low_filt over the first group, k_search_low_next over the others.
 static bool several_groups_ok(const Snapshot* snap)
 {
-    if (snap->n_group < 2u || snap->n_group > QS_MAX_GROUPS || ctx_opt(snap->ctx, OPT_GROUPS_WG) != 1) return false;
+    const int64_t groups_wg = ctx_opt(snap->ctx, OPT_GROUPS_WG);
+    if (snap->n_group < 2u || snap->n_group > QS_MAX_GROUPS || (groups_wg != 1 && groups_wg != 2)) return false;
     for (uint32_t i = 0; i < snap->n_group; ++i)
         if (!snap->groups[i]->packed || snap->h_group[i].win_lo != 0u || snap->h_group[i].win_hi != 0xFFFFFFFFu) return false;
     return true;
+}
+static bool several_groups_low_ok(const Ctx* ctx, bool any_filtered)
+{
+    return ctx_opt(ctx, OPT_GROUPS_WG) == 2 && low_floors_ok(ctx, any_filtered);
 }
 static bool takes_query_wg(const Snapshot* snap, const uint64_t* offsets, const fpx_opts* opts, uint32_t B, bool* filt, bool* low)
 {
@@ -728,7 +737,7 @@ static bool takes_query_wg(const Snapshot* snap, const uint64_t* offsets, const 
         *filt = false;
         for (uint32_t i = 0; i < snap->n_group; ++i) *filt = *filt || group_filtered(snap->h_group[i]);
         *low = false;
-        return (!*filt || query_wg == 2) && queries_fit_wg(offsets, opts, B);
+        return (!*filt || query_wg == 2) && queries_fit_wg(offsets, opts, B, several_groups_low_ok(snap->ctx, *filt), low);
     }
     if (!snap->groups[0]->packed) return false;
     *filt = group_filtered(snap->h_group[0]);
@@ -808,6 +817,16 @@ static void launch_search_next(bool ns8, bool qs, bool filt, dim3 grid, hipStrea
     else { if (qs) FPX_LN_FILT(16, true); else FPX_LN_FILT(16, false); }
 #undef FPX_LN_FILT
 #undef FPX_LN
+}
+// ... and k_search_low_next's (the same for a batch with queries whose floor is 1 or 2: option groups_wg = 2 with low_wg)
+static void launch_search_low_next(bool ns8, bool qs, bool filt, dim3 grid, hipStream_t st, const QSearchArgs& qa, const GroupArgs& g)
+{
+#define FPX_LLN(NS, QSV, FILT) hipLaunchKernelGGL((k_search_low_next<NS, QSV, FILT>), grid, dim3(QS_WG), QS_LDS_BYTES, st, qa, g)
+#define FPX_LLN_FILT(NS, QSV) do { if (filt) FPX_LLN(NS, QSV, true); else FPX_LLN(NS, QSV, false); } while (0)
+    if (ns8) { if (qs) FPX_LLN_FILT(8, true); else FPX_LLN_FILT(8, false); }
+    else { if (qs) FPX_LLN_FILT(16, true); else FPX_LLN_FILT(16, false); }
+#undef FPX_LLN_FILT
+#undef FPX_LLN
 }
 // a query-per-workgroup path opens: the queries' candidate slots (`extra_words` of the caller's behind them), the counters and statistics
 // sets zeroed, the probe's first event -- and the arguments every such kernel takes, from the batch (Args: QFrameArgs | QSearchArgs,
@@ -891,7 +910,8 @@ static int redo_hot_queries(Batch& b, QSearchArgs qa, const GroupArgs& gargs, bo
 // SEVERAL GROUPS (option groups_wg = 1; takes_query_wg): per upload piece the groups are walked one after the other on the batch's stream --
 // k_search_query over group 0 (with the memory segments' table), k_search_next over groups 1.., which chain their candidates behind the
 // launch before (fpx_qsearch.hpp).  The batch is opened once and closed once, one k_finish; a hand-back from any launch is the batch's.
-// No redo list and no low floors there; filt: ANY group is filtered -- which instantiation a launch is is its own group's business.
+// No redo list there; filt: ANY group is filtered -- which instantiation a launch is is its own group's business.  Low floors under
+// groups_wg = 2 only (with low_wg): k_search_low or k_search_low_filt over group 0, k_search_low_next over the others, path bits 13 and 12.
 static_assert(QS_MAX_GROUPS * Workspace::UP_CHUNKS <= DEF_COUNT_STRIDE, "the launches' next_q words -- one per (upload piece, group) -- are the first deferred-list count's line, which k_qs_zero clears");
 static int run_query_wg(Batch& b, bool filt, bool low)
 {
@@ -903,10 +923,12 @@ static int run_query_wg(Batch& b, bool filt, bool low)
     if (low) {
         // (a query with a low floor hands over up to max_results candidates -- the legacy protocol's 500 --, all of them through the shared
         // list once they are more than its slots: the list is sized for that, not for the first guess of 64 per query)
+        // (several groups: every launch hands over its own group's top max_results -- up to that many again per group; the slots a
+        // launch carries over into the list were counted with the group that filled them)
         size_t want = 0;
         for (uint32_t q = 0; q < B; ++q) {
             const bool low_q = query_floor(b.opts[q], b.offsets[q + 1] - b.offsets[q]) <= 2u;
-            want += low_q ? std::min<size_t>(b.opts[q].max_results, QS_REC_CAP) + 32u : 64u;
+            want += low_q ? (size_t)ngroups * (std::min<size_t>(b.opts[q].max_results, QS_REC_CAP) + 32u) : 64u;
         }
         if (ws->cap_cands < want && (rc = grow_pair(ws->d_cands, &ws->cap_cands, want))) return rc;
     }
@@ -937,13 +959,20 @@ static int run_query_wg(Batch& b, bool filt, bool low)
         if (up_chunks) FPX_HIP(hipStreamWaitEvent(st, ws->ev_chunk[c], 0));           // (the piece's hashes have arrived; the next piece is on its way)
         const dim3 grid(std::min<uint32_t>(qa.q_end - qa.q_begin, (uint32_t)cus * QS_WGS_PER_CU));
         if (ngroups > 1u) {
-            // (the piece's queries over group 0, then over every other group: a launch's queue of queries is a word of its own)
-            launch_search_query(ns8, b.want_q, qa.mem_tab != nullptr, group_filtered(snap->h_group[0]), grid, st, qa, gargs);
+            // (the piece's queries over group 0, then over every other group: a launch's queue of queries is a word of its own.
+            // low -- option groups_wg = 2 --: the kernels with the sorted tail, each launch filtered or not as its own group is)
+            const bool filt0 = group_filtered(snap->h_group[0]);
+            if (low && filt0) launch_search_low_filt(ns8, b.want_q, qa.mem_tab != nullptr, grid, st, qa, gargs);
+            else if (low) launch_search_low(ns8, b.want_q, qa.mem_tab != nullptr, grid, st, qa, gargs);
+            else launch_search_query(ns8, b.want_q, qa.mem_tab != nullptr, filt0, grid, st, qa, gargs);
             QSearchArgs qn = qa;
             qn.mem_tab = nullptr; qn.mem_bucket = nullptr; qn.mem_bits = nullptr;
             for (uint32_t gi = 1; gi < ngroups; ++gi) {
                 qn.next_q = qa.next_q ? ws->d_def_count + (size_t)gi * Workspace::UP_CHUNKS + c : nullptr;
-                launch_search_next(snap->groups[gi]->ns == 8u, b.want_q, group_filtered(snap->h_group[gi]), grid, st, qn, GroupArgs{snap->h_group[gi], snap->d_direct});
+                const bool ns8_g = snap->groups[gi]->ns == 8u, filt_g = group_filtered(snap->h_group[gi]);
+                const GroupArgs gargs_g{snap->h_group[gi], snap->d_direct};
+                if (low) launch_search_low_next(ns8_g, b.want_q, filt_g, grid, st, qn, gargs_g);
+                else launch_search_next(ns8_g, b.want_q, filt_g, grid, st, qn, gargs_g);
                 ++next_launches;
             }
         }
@@ -1793,8 +1822,9 @@ static bool parts_take(const Snapshot* snap, const uint64_t* offsets, const fpx_
     const bool packed = p0->groups[0]->packed;
     if (query_wg != 2 && filtered) return false;
     if (bits_for(B) > 24u || offsets[B] == offsets[0]) return false;
-    // (a part 0 of several groups -- made under groups_wg -- while that option allows it, and for batches without low floors)
-    if (p0->n_group > 1u) return several_groups_ok(p0) && queries_fit_wg(offsets, opts, B);
+    // (a part 0 of several groups -- made under groups_wg -- while that option allows it; batches with low floors under groups_wg 2
+    // with low_wg only: takes_query_wg's rule)
+    if (p0->n_group > 1u) return several_groups_ok(p0) && queries_fit_wg(offsets, opts, B, several_groups_low_ok(snap->ctx, filtered));
     // (floors of 1 and 2: takes_query_wg's rule -- option low_wg, a packed part 0; a filtered one under 2 only)
     return queries_fit_wg(offsets, opts, B, packed && low_floors_ok(snap->ctx, filtered));
 }

@@ -65,10 +65,11 @@ class Context:
         floors of queries of 40 hashes or fewer) is the pipeline's | stays on the query-per-workgroup path of a packed, unfiltered group:
         such queries' records are sorted in LDS and only what finish can return is handed over (Stats.path_flags bit 12, with bits 6
         and 2; 'hot_wg' is ignored for such a batch) | as 1, and on a group with superseded docs or masked columns too, which only
-        'query_wg' 2 puts on that path (bits 12 and 8).  'groups_wg': 0 | 1 -- a snapshot of several packed groups keeps the largest for
+        'query_wg' 2 puts on that path (bits 12 and 8).  'groups_wg': 0 | 1 | 2 -- a snapshot of several packed groups keeps the largest for
         the query-per-workgroup path and sends the others through the pipeline | walks up to 8 of them one after the other a query per
         workgroup, one finish (Stats.path_flags bit 13, with bits 6 and 2; read when a snapshot is made as well: part 0 of a snapshot in
-        two parts then holds all such groups)"""
+        two parts then holds all such groups) | as 1, and a batch with queries whose score floor is 1 or 2 is walked that way too where
+        'low_wg' allows it -- 1 when no group is filtered, 2 also when any is -- (bits 13 and 12 together)"""
         check(lib().fpx_ctx_set_option(self.h, name.encode(), int(value)))
 
     def trim(self):

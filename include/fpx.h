@@ -98,7 +98,9 @@ typedef struct {
                                    filtered -- k_search_low_filt, "low_wg" 2 under "query_wg" 2),
                                    bit 13: the batch (or its part 0) walked SEVERAL packed groups a query per workgroup, one after the
                                    other -- k_search_query over the first, k_search_next over the others, one k_finish ("groups_wg" 1;
-                                   bits 6 and 2 are set with it, and bit 8 when any of the groups is filtered) */
+                                   bits 6 and 2 are set with it, and bit 8 when any of the groups is filtered).  Bits 13 and 12
+                                   together ("groups_wg" 2 with "low_wg"): the batch has queries with a floor of 1 or 2 -- k_search_low
+                                   (k_search_low_filt) over the first group, k_search_low_next over the others */
     uint64_t probe_kernel_fetched_bytes; /* block bytes the main probe kernel really fetched, in 128-byte lines: a probe
                                    whose hash the segment's presence bits know to be absent counts as a visited block (as in
                                    the reference) without the block being read, and a block that is read costs two lines up
@@ -164,7 +166,7 @@ int  fpx_ctx_device(const fpx_ctx *ctx);     /* the HIP ordinal the context live
  *                        so does such a batch on a FILTERED group -- superseded docs and/or columns outside the snapshot, which
  *                        "query_wg" 2 alone puts on this path; with "query_wg" 1 the value 2 is 1 --, by k_search_low_filt (bits 12
  *                        and 8): the filtered walk leaves live docs only for the same sorted tail.  On an unfiltered group 2 is 1
- *   "groups_wg"          0 | 1   a snapshot of SEVERAL packed groups -- an index with more dense segments than one group's 16 columns,
+ *   "groups_wg"          0 | 1 | 2   a snapshot of SEVERAL packed groups -- an index with more dense segments than one group's 16 columns,
  *                        merge results that met and formed a group of their own -- keeps its largest group for k_search_query (part 0
  *                        of two parts) and sends the others through the pipeline; a snapshot that is nothing but such groups is the
  *                        pipeline's whole (default 0) | walks 2 .. 8 packed groups ONE AFTER THE OTHER a query per workgroup: a doc
@@ -176,7 +178,14 @@ int  fpx_ctx_device(const fpx_ctx *ctx);     /* the HIP ordinal the context live
  *                        array of 8192 in ANY group hands the batch to the pipeline, with the back-off.  Read when a snapshot is
  *                        made too: part 0 of a snapshot in two parts then holds every packed group that could have been part 0
  *                        alone (up to 8, largest first); with nothing left for part 1 the snapshot has no parts and is taken whole.
- *                        One packed group behaves exactly as under 0
+ *                        One packed group behaves exactly as under 0 | 2: as 1, and a batch WITH queries whose floor is 1 or 2 is
+ *                        walked that way too where "low_wg" allows it -- "low_wg" 1 when no group is filtered, 2 also when any is
+ *                        (under "query_wg" 2) --: k_search_low (k_search_low_filt on a filtered group) over the first group, with
+ *                        the memory segments' table, k_search_low_next over the others (bits 13 and 12 together).  Every launch
+ *                        sorts such a query's records of its own group, raises the floor by that group's best score -- a lower bound
+ *                        of the one k_finish applies -- and hands over the group's top max_results: their union holds the
+ *                        snapshot's.  With "low_wg" 0, or a filtered group under "low_wg" 1, such a batch is the pipeline's as
+ *                        under 1; a batch without such a query runs exactly what it runs under 1
  *   "fast"              1 | 0   the device-sized path (one host round trip per batch; default 1)
  *   "binned"             1 | 0   groups drop their records into bins of a few queries, scored a bin per workgroup (default 1)
  *   "rec32"              1 | 0   4-byte records in the bins where the doc ids leave room (default 1)
