@@ -384,6 +384,7 @@ enum CtxOpt : int {
     OPT_WORDS_WG,
     OPT_LOW_WG,
     OPT_GROUPS_WG,
+    OPT_SHARD_WG,
     OPT_COUNT
 };
 constexpr int64_t OPT_UNSET = -2;
@@ -505,6 +506,7 @@ int score_records_impl(Ctx* ctx, const QueryBatch* qb, const uint64_t* d_records
 uint64_t group_bytes_lower_bound(const Ctx* ctx, Segment* const* segs, uint32_t k);
 constexpr uint32_t SHARD_DEDUP_MAX = 2048;      // = DEDUP_MAX (fpx_kernels_common.hpp): the routed keys' queries hold at most this many hashes
 int shard_bins_per_rank(uint32_t B, uint32_t world);
+bool shard_window_walk_ok(const Snapshot* snap);      // option shard_wg: fpx_shard_probe would walk this snapshot's window a query per workgroup (but for the back-off)
 int shard_probe_impl(Snapshot* snap, const QueryBatch* qb, uint32_t world, uint32_t timeout_ms,
                      uint64_t* d_send, uint64_t cell_cap, uint32_t* d_send_counts, uint64_t* needed_cell_cap, fpx_stats* stats);
 int shard_score_impl(Ctx* ctx, const QueryBatch* qb, uint32_t world, uint32_t rank, const uint64_t* d_recv, uint64_t cell_cap, const uint32_t* d_recv_counts,

@@ -41,6 +41,8 @@
 // Option groups_wg = 1: a snapshot of several packed groups is walked group by group, k_search_next over the groups behind the first;
 // groups_wg = 2: as 1, and with low_wg a batch with floors of 1 or 2 too -- k_search_low (k_search_low_filt) over the first group,
 // k_search_low_next over the others.
+// Option shard_wg = 1 (fpx_shard_probe, a step of the sharded bin protocol): a rank's hash-window slice of a packed group is walked by
+// k_search_window -- the same body, `SHARE` --, the query's records copied into its bin instead of counted; 2: a filtered slice too.
 // FILT (option query_wg = 2): the same for a group with superseded docs and/or columns outside the snapshot (a live index between a
 // merge and its regroup) -- every word knows its column, as in k_probe_pgroup's per-column walk: a column outside `active` gives no
 // record and no statistic, a doc of a column with a dead set is dropped after it was counted (CTR_DOCS counts before supersession).
@@ -116,6 +118,10 @@ struct QSearchArgs {
     // (option hot_wg = 1, unfiltered) the batch's redo list, or null: a query whose records outgrow the LDS array is named here --
     // q | its record total << 32, through CTR_REDO -- for k_search_classes instead of failing the batch (redo_cap: entries the list takes)
     unsigned long long* redo; uint32_t redo_cap;
+    // k_search_window (SHARE) has no candidates, no slots and no redo list, and CARRIES THE STEP'S BINS IN THOSE MEMBERS -- the struct, and with
+    // it every other kernel's argument offsets, stays as it is: cands = the bins ([bin][cand_cap] records, 4 or 8 bytes each), cand_cap = a
+    // bin's capacity in RECORDS, qcand_n = the bins' fill counters (BIN_STRIDE words apart), redo_cap = 1: 4-byte records (bin_record32),
+    // 0: 8-byte ones; qcand and redo are null.
 };
 
 // The kernel's arguments as its two by-value parameters lay them out in the kernel-argument segment.  Most of them are needed once per
@@ -234,9 +240,16 @@ constexpr uint32_t QS_LOW_CHUNK = 8;              // (LOW) records a lane sorts 
 // ... and a sixth: k_search_low_next (LOW and NEXT true, below; option groups_wg = 2 with low_wg) -- a later group's walk for a batch
 // with floors of 1 or 2: the sorted tail's candidates -- each group's top max_results under its own raised floor, a superset of what
 // k_finish keeps of the group -- go through the same buffer, flags and shared list into the chained hand-over.
-template <int NS, bool QS, bool MEM, bool FILT, bool CLS, bool LOW = false, bool NEXT = false>
+// ... and a seventh: k_search_window (SHARE true, below; option shard_wg) -- the same walk over a rank's HASH-WINDOW slice of a group, for
+// a step of the sharded bin protocol (fpx_search.hip: shard_probe_impl).  The dedup loop's window test leaves the other windows' hashes to
+// their ranks; what a rank owes the protocol is the query's RECORDS, not its counts -- they go to the query's bin of 2^QS_SHARE_BQ queries
+// in the caller's send buffer, in bin_store's form (fpx_partition.hpp), one reservation per query.  No filter, no table, no candidates.
+constexpr uint32_t QS_SHARE_BQ = 3;               // (SHARE) queries per bin: fpx_search.hip's SHARD_BQ
+constexpr uint32_t QS_SHARE_STRIDE = 32;          // (SHARE) 32-bit words between the bins' fill counters: fpx_partition.hpp's BIN_STRIDE
+template <int NS, bool QS, bool MEM, bool FILT, bool CLS, bool LOW = false, bool NEXT = false, bool SHARE = false>
 __device__ __forceinline__ void qs_body(const QSearchArgs& a, const GroupArgs& ga)
 {
+    static_assert(!SHARE || (!QS && !CLS && !LOW && !NEXT), "a window's walk for the bin protocol: no per-query statistics, no doc classes, no sorted tail, one group");
     static_assert(!NEXT || (!CLS && !MEM), "a later group's walk: no doc classes, no memory table (they ride on the first group's launch)");
     static_assert(!(CLS && FILT), "doc classes: the unfiltered walk only");
     static_assert(!LOW || (!CLS && QS_WG == 256u && QS_REC_CAP >= 512u && (QS_REC_CAP & (QS_REC_CAP - 1u)) == 0u),
@@ -1056,8 +1069,10 @@ __device__ __forceinline__ void qs_body(const QSearchArgs& a, const GroupArgs& g
     }
 
     // (every task has been read: the queue's slots become the filter and the exact table)
+    if constexpr (!SHARE) {
     for (uint32_t i = tid; i < (1u << (QS_FLOG2 - 1u)); i += QS_WG) filter[i] = 0u;
     for (uint32_t s = tid; s < T; s += QS_WG) table[s] = 0ull;
+    }
     // ---- the query's statistics (what FileSegment.search observes per hash, summed: src/FileSegment.zig:177-178)
     {
         auto wave_total = [&](uint32_t v) -> unsigned long long {
@@ -1093,6 +1108,7 @@ __device__ __forceinline__ void qs_body(const QSearchArgs& a, const GroupArgs& g
     // ---- SearchResults.incr (src/common.zig:121-129), first the filter: every record into its doc's cell
     // (four records per lane and turn, read as one 16-byte piece: the loop is a chain of LDS latencies -- a record, then its cell)
     // (a lane's four are all records in every turn but the query's last: only that one tests record by record)
+    if constexpr (!SHARE)
     for (uint32_t i = tid * 4u; i < nrec; i += QS_WG * 4u) {
         const uint4 r4 = *reinterpret_cast<const uint4*>(recs + i);             // (the array ends with four spare words)
         const uint32_t r[4] = {r4.x, r4.y, r4.z, r4.w};
@@ -1117,7 +1133,7 @@ __device__ __forceinline__ void qs_body(const QSearchArgs& a, const GroupArgs& g
     // (the tasks beyond the queue were never read) and would overflow the same queue in every class: that one fails the batch as before.
     const bool q_stats = !CLS || cls == 0u;                  // (CLS: blocks, docs, probes, reads and the histograms in one pass only)
     bool q_redo = false;
-    if constexpr (!FILT && !CLS && !NEXT) {
+    if constexpr (!FILT && !CLS && !NEXT && !SHARE) {      // (SHARE: no redo list -- the member carries something else)
         if (s_over_recs != 0u || s_count > QS_REC_CAP) q_redo = kt->a.redo != nullptr && s_ntask <= TCAP;
     }
     if (tid == 0 && q_redo) {
@@ -1307,6 +1323,40 @@ __device__ __forceinline__ void qs_body(const QSearchArgs& a, const GroupArgs& g
         }
       }
     }
+    if constexpr (SHARE) {
+        // ---- (SHARE) the query's records of this window leave for its bin, bin q >> QS_SHARE_BQ of the step's send buffer -- the members
+        //      this kernel has no other use for carry it (QSearchArgs): cands the bins, cand_cap a bin's capacity in records, qcand_n the
+        //      bins' fill counters, redo_cap the record width.  ONE reservation per query -- nrec is final: the barrier above --, the base
+        //      to the workgroup through LDS; every lane copies.  A place at or beyond the capacity is not stored, the fill counter runs
+        //      past it: k_cell_counts and the host learn the need from it.  The record is bin_store's (fpx_partition.hpp): narrow,
+        //      doc << 3 | q & 7 -- a doc that leaves no room, or would read as "no record", raises CTR_BINFAIL to 3 and the host redoes
+        //      the step wide --; wide, q << 32 | doc.  A query whose records outgrew the array (or whose task queue overflowed) stores
+        //      nothing: CTR_BINFAIL is 1 (the statistics above) and the host redoes the step on the pipeline.  No padding.
+        (void)floor_q; (void)smax; (void)low_q; (void)filter; (void)table; (void)cbuf; (void)TMASK;
+        if (s_over_recs == 0u && s_count <= QS_REC_CAP && nrec != 0u) {      // (uniform: LDS words behind a barrier)
+            const uint32_t bn = q >> QS_SHARE_BQ;
+            if (tid == 0) s_cbase_lo = atomicAdd(&kt->a.qcand_n[(size_t)bn * QS_SHARE_STRIDE], nrec);
+            __syncthreads();
+            const uint64_t base = s_cbase_lo, cap = kt->a.cand_cap;
+            const uint32_t gmin_c = kt->ga.g.gmin;
+            if (kt->a.redo_cap != 0u) {                                        // (uniform)
+                uint32_t* const dst = reinterpret_cast<uint32_t*>(kt->a.cands) + (size_t)bn * cap;
+                bool wide = false;
+                for (uint32_t i = tid; i < nrec; i += QS_WG) {
+                    const uint32_t doc = recs[i] + gmin_c;
+                    if (base + i < cap) {
+                        wide = wide || (doc >> (32u - QS_SHARE_BQ)) != 0u || doc == (0xFFFFFFFFu >> QS_SHARE_BQ);
+                        dst[base + i] = (doc << QS_SHARE_BQ) | (q & ((1u << QS_SHARE_BQ) - 1u));
+                    }
+                }
+                if (wide) atomicMax(&kt->a.counters[CTR_BINFAIL], 3ull);
+            } else {
+                uint64_t* const dst = kt->a.cands + (size_t)bn * cap;
+                for (uint32_t i = tid; i < nrec; i += QS_WG)
+                    if (base + i < cap) dst[base + i] = ((uint64_t)q << 32) | (uint32_t)(recs[i] + gmin_c);
+            }
+        }
+    } else
     if (!low_q && s_over_recs == 0u && !q_redo && nrec != 0u && nrec >= floor_q) {
         if (tid == 0) { s_claimed = 0u; s_full = 0u; }
         __syncthreads();                                // (the filter's counts are complete behind this barrier)
@@ -1403,7 +1453,10 @@ __device__ __forceinline__ void qs_body(const QSearchArgs& a, const GroupArgs& g
     __syncthreads();
     QS_MARK(4);
     const uint32_t cn = min(s_ccnt, SB_CAND);
-    if constexpr (NEXT) {
+    (void)cn;
+    if constexpr (SHARE) {
+        // (no candidates: the query's slots and their count are not this kernel's -- the members carry the bins)
+    } else if constexpr (NEXT) {
         const qs_kargs_t kh = qs_cold_args();
         // ---- (NEXT) the CHAINED hand-over.  prev: what the launch before on this stream left for the query -- a kernel boundary lies
         //      between, a plain load sees it.  (1) prev overflowed: this launch's candidates follow the others into the shared list, the
@@ -1545,6 +1598,18 @@ template <int NS, bool QS, bool FILT>
 __global__ __launch_bounds__(QS_WG) FPX_QS_OCC void k_search_low_next(QSearchArgs a, GroupArgs ga)
 {
     qs_body<NS, QS, false, FILT, false, true, true>(a, ga);
+}
+
+// k_search_window (option shard_wg): k_search_query's body over a rank's hash-window slice of ONE packed group, for a step of the sharded
+// bin protocol (qs_body: `SHARE`) -- the walk as it stands, the window test in its dedup loop, and in place of the counting tail the
+// query's records copied into its bin of the caller's send buffer.  MEM: the memory segments' table (the same on every rank; only the
+// window's hashes are looked up).  FILT (option shard_wg = 2): a slice with superseded docs or columns outside the snapshot -- live docs
+// only reach the record array.  No per-query statistics (fpx_shard_probe has none), no redo list, no low floors (the record protocol
+// keeps them).  The same two by-value parameters: qs_cold_args()'s layout holds.
+template <int NS, bool MEM, bool FILT>
+__global__ __launch_bounds__(QS_WG) FPX_QS_OCC void k_search_window(QSearchArgs a, GroupArgs ga)
+{
+    qs_body<NS, false, MEM, FILT, false, false, false, true>(a, ga);
 }
 
 // zeroes what a batch of k_search_query adds to: the batch's counters and the statistics sets (one launch instead of two memsets)

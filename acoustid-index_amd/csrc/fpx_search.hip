@@ -828,6 +828,16 @@ static void launch_search_low_next(bool ns8, bool qs, bool filt, dim3 grid, hipS
 #undef FPX_LLN_FILT
 #undef FPX_LLN
 }
+// ... and k_search_window's (a rank's hash-window slice, a step of the sharded bin protocol: option shard_wg)
+static void launch_search_window(bool ns8, bool mem, bool filt, dim3 grid, hipStream_t st, const QSearchArgs& qa, const GroupArgs& g)
+{
+#define FPX_LW(NS, MEM, FILT) hipLaunchKernelGGL((k_search_window<NS, MEM, FILT>), grid, dim3(QS_WG), QS_LDS_BYTES, st, qa, g)
+#define FPX_LW_FILT(NS, MEM) do { if (filt) FPX_LW(NS, MEM, true); else FPX_LW(NS, MEM, false); } while (0)
+    if (ns8) { if (mem) FPX_LW_FILT(8, true); else FPX_LW_FILT(8, false); }
+    else { if (mem) FPX_LW_FILT(16, true); else FPX_LW_FILT(16, false); }
+#undef FPX_LW_FILT
+#undef FPX_LW
+}
 // a query-per-workgroup path opens: the queries' candidate slots (`extra_words` of the caller's behind them), the counters and statistics
 // sets zeroed, the probe's first event -- and the arguments every such kernel takes, from the batch (Args: QFrameArgs | QSearchArgs,
 // by their same-named members; which queries a launch takes is the caller's to say)
@@ -2214,6 +2224,19 @@ static unsigned log2_exact(uint32_t v) { unsigned b = 0; while ((1u << b) < v) +
 static unsigned shard_sort_bits(unsigned win_bits) { return win_bits >= 8u ? 0u : 8u - win_bits; }
 
 static_assert(SHARD_DEDUP_MAX == DEDUP_MAX, "fpx_sharded.hip routes longer queries to the record protocol");
+static_assert(QS_SHARE_BQ == SHARD_BQ && QS_SHARE_STRIDE == BIN_STRIDE && DEDUP_MAX <= QS_MAX_HASHES, "k_search_window fills the protocol's bins");
+// Option shard_wg: would a step of the bin protocol on this snapshot WALK ITS WINDOW A QUERY PER WORKGROUP (k_search_window, fpx_qsearch.hpp)?
+// ONE packed group with its hash window and nothing else -- or that plus memory segments behind their one table --, unfiltered (1) or
+// filtered too (2).  (The caller has refused solo and block segments and memory segments without a table.)  The back-off after a
+// hand-back, snap->qs_skip, is the caller's to look at: it counts calls.
+bool shard_window_walk_ok(const Snapshot* snap)
+{
+    const int64_t shard_wg = ctx_opt(snap->ctx, OPT_SHARD_WG);
+    if (shard_wg != 1 && shard_wg != 2) return false;
+    if (snap->n_group != 1 || snap->n_solo != 0 || snap->n_file != 0 || !snap->groups[0]->packed) return false;
+    if (snap->n_mem != 0 && snap->mem_items != 0 && !snap->d_memtab) return false;
+    return shard_wg == 2 || !group_filtered(snap->h_group[0]);
+}
 // bins per rank: the batch's bins of 2^SHARD_BQ queries, dealt to the ranks in contiguous runs
 int shard_bins_per_rank(uint32_t B, uint32_t world)
 {
@@ -2285,11 +2308,54 @@ int shard_probe_impl(Snapshot* snap, const QueryBatch* qb, uint32_t world, uint3
         uint32_t stride = (uint32_t)std::min<uint64_t>(max_len, (uint64_t)((double)max_len * share * 1.25) + 48);
         const bool rec32_enabled = ctx_opt(snap->ctx, OPT_REC32) != 0;
         uint64_t rec_cap = cell_cap;                           // records a bin's cells hold
+        // option shard_wg: the window walked a query per workgroup (k_search_window) -- no keys, one launch.  After a hand-back the
+        // snapshot's next 32 calls do not try (qs_skip, as on one GPU)
+        bool walk = shard_window_walk_ok(snap), walked = false;
+        if (walk) {
+            const uint32_t skip = __atomic_load_n(&snap->qs_skip, __ATOMIC_RELAXED);
+            if (skip != 0u) { __atomic_store_n(&snap->qs_skip, skip - 1u, __ATOMIC_RELAXED); walk = false; }
+        }
         for (int attempt = 0;; ++attempt) {
             // 4-byte records (two per 8-byte cell) where the doc ids leave room for the query's three bits inside its bin
             const uint32_t rec32 = rec32_enabled && !__atomic_load_n(&snap->rec32_refused, __ATOMIC_RELAXED) &&
                                    snap->max_doc_declared < (0xFFFFFFFFu >> SHARD_BQ) ? 1u : 0u;
             rec_cap = cell_cap << rec32;
+            if (walk) {
+                FPX_HIP(hipMemsetAsync(ws->d_cells, 0, words * sizeof(uint32_t), st));
+                FPX_HIP(hipMemsetAsync(ws->d_counters, 0, CTR_COUNT * sizeof(unsigned long long), st));
+                QSearchArgs qa{};
+                qa.hashes_base = qb->d_hashes; qa.offsets = qb->d_offsets; qa.opts = qb->d_opts; qa.q_begin = 0u; qa.q_end = B; qa.sb = 32u - qbits;
+                qa.counters = ws->d_counters; qa.stat_sets = reinterpret_cast<unsigned long long*>(d_stats32); qa.qstats = nullptr; qa.cancel = cancel;
+                if (snap->n_mem != 0 && snap->mem_items != 0) { qa.mem_tab = snap->d_memtab; qa.mem_bucket = snap->d_membucket; qa.mem_bits = snap->d_membits; }
+                // (the bins ride in the members k_search_window has no other use for: QSearchArgs)
+                qa.cands = d_send; qa.cand_cap = rec_cap; qa.qcand = nullptr; qa.qcand_n = ws->d_cells; qa.redo = nullptr; qa.redo_cap = rec32;
+                // (the launch's queue of queries: a word behind the overflow flag, zeroed with the cells)
+                qa.next_q = FPX_QS_DYN ? d_overflow + 4 : nullptr; qa.stagger = 0u;
+                const GroupArgs gargs{snap->h_group[0], snap->d_direct};
+                const dim3 grid(std::min<uint32_t>(B, (uint32_t)device_cus(snap->ctx) * QS_WGS_PER_CU));
+                FPX_HIP(hipEventRecord(ws->ev_probe0, st));
+                launch_search_window(snap->groups[0]->ns == 8u, qa.mem_tab != nullptr, group_filtered(snap->h_group[0]), grid, st, qa, gargs);
+                FPX_HIP(hipEventRecord(ws->ev_probe1, st));
+                hipLaunchKernelGGL(k_cell_counts, dim3((ncells + 255) / 256), dim3(256), 0, st, (const unsigned int*)ws->d_cells, ncells, d_send_counts, ws->d_counters,
+                                   rec32 << 31);
+                FPX_HIP(hipGetLastError());
+                FPX_HIP(hipMemcpyAsync(ws->h_counters, ws->d_counters, CTR_COUNT * sizeof(unsigned long long), hipMemcpyDeviceToHost, st));
+                FPX_HIP(hipMemcpyAsync(ws->h_cells, d_stats32, (LEAN_STAT_WORDS + 16) * sizeof(uint32_t), hipMemcpyDeviceToHost, st));
+                FPX_SYNC(ws);
+                if (ws->h_counters[CTR_BINFAIL] == 3 && attempt < 3) {            // a doc id beyond the segments' declared range: wide records
+                    __atomic_store_n(&snap->rec32_refused, 1u, __ATOMIC_RELAXED);
+                    continue;
+                }
+                if (ws->h_counters[CTR_BINFAIL] != 0) {
+                    // a query's records outgrew the workgroup's array (or its task queue): the pipeline below answers this call, and the
+                    // snapshot's next 32 too
+                    __atomic_store_n(&snap->qs_skip, 32u, __ATOMIC_RELAXED);
+                    walk = false; attempt = -1;
+                    continue;
+                }
+                walked = true;
+                break;
+            }
             const uint64_t P = (uint64_t)B * stride;
             if ((rc = grow_pair(ws->d_keys, &ws->cap_keys, (size_t)P + 1))) return rc;
             FPX_HIP(hipMemsetAsync(ws->d_cells, 0, words * sizeof(uint32_t), st));
@@ -2385,6 +2451,11 @@ int shard_probe_impl(Snapshot* snap, const QueryBatch* qb, uint32_t world, uint3
             stats->algorithmic_bytes = blocks * 512ull + bytes_off; stats->probe_kernel_bytes = blocks * 512ull + bytes_off;
             stats->probe_kernel_fetched_bytes = dreads * 64ull; stats->probe_kernel_ms = ms; stats->total_gpu_ms = ms; stats->probe_launches = 1;
             stats->path_flags = 1u | 4u | 8u | 16u;
+            if (walked) {       // (k_search_window's sets, read the way finish_wg_path reads k_search_query's; bit 14: fpx.h)
+                stats->hits = s.records;
+                stats->probe_kernel_fetched_bytes = (dreads + 1) / 2 * 128ull;
+                stats->path_flags |= 64u | 16384u;
+            }
         }
         return FPX_OK;
     };

@@ -830,6 +830,39 @@ static int windows_search_batch(ShardedSnapshot* ss, const uint32_t* hashes, con
         });
         return first_error();
     };
+    // ---- the bin protocol with EVERY RANK WALKING ITS WINDOW a query per workgroup (option shard_wg; fpx_search.hip: shard_probe_impl,
+    //      k_search_window): every rank gets the WHOLE batch, dedups each query and walks the hashes of its window, the query's records
+    //      copied into its bin -- no keys are made or routed, no all-to-all #1.  The bins, their exchange and the finish are the routed
+    //      body's; a rank whose walk handed the step back to its pipeline inside shard_probe_impl looks like any other from here.
+    auto body_walk = [&]() -> int {
+        int r;
+        run_all([&](uint32_t k) -> int { return query_batch_create_impl(ss->ctxs[k], hashes, offsets, B, opts, &shares[k]); });
+        if ((r = first_error())) return r;
+        uint64_t cell_cap = std::max<uint64_t>(ss->cell_cap.load(), 2048);
+        for (int attempt = 0;; ++attempt) {
+            if ((r = win_reserve_bins(ss, b, bpr, cell_cap))) return r;
+            run_all([&](uint32_t k) -> int {
+                return shard_probe_impl(ss->locals[k], shares[k], n, timeout_ms, b->bins_send[k], b->cell_cap, b->bcnt_send[k], &needs[k], &sts[k]);
+            });
+            r = first_error();
+            if (r == FPX_OK) break;
+            if (r != FPX_E_AGAIN || attempt >= 3) return r == FPX_E_AGAIN ? FPX_E_DEVICE : r;
+            for (uint32_t k = 0; k < n; ++k) cell_cap = std::max(cell_cap, needs[k]);      // (one size for all ranks: this process sees every need)
+        }
+        ss->cell_cap.store(b->cell_cap);
+        {
+            const A2APart parts[2] = {a2a_part(b->bins_send, b->bins_recv, (size_t)bpr * b->cell_cap * sizeof(uint64_t)), a2a_part(b->bcnt_send, b->bcnt_recv, (size_t)bpr * sizeof(uint32_t))};
+            if ((r = win_all_to_all(ss, b, parts, 2))) return r;
+        }
+        if (timeout_ms && std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t_call).count() > (double)timeout_ms) { set_error("search timeout"); return FPX_E_TIMEOUT; }
+        // ---- every rank finishes the queries of its bins (the whole-batch form, fpx_shard_score's): straight into the caller's rows
+        run_all([&](uint32_t k) -> int {
+            if (q_hi[k] == q_lo[k]) return FPX_OK;
+            return shard_score_impl(ss->ctxs[k], shares[k], n, k, b->bins_recv[k], b->cell_cap, b->bcnt_recv[k], timeout_ms,
+                                    out ? out + (size_t)q_lo[k] * out_cap : nullptr, out_cap, out_n + q_lo[k], nullptr, nullptr, nullptr, 0u);
+        });
+        return first_error();
+    };
     // ---- the RECORD protocol, for what the bins do not take: a batch with a score floor of 1 or 2 (the legacy front end searches
     //      with limit = max_results, min_score = 1: src/legacy.zig:185-196 -- nearly every counted doc is a candidate) or with queries of
     //      more than DEDUP_MAX hashes.  Every rank probes ITS window with the whole batch (fpx_probe_resident: the records grouped by the
@@ -934,7 +967,10 @@ static int windows_search_batch(ShardedSnapshot* ss, const uint32_t* hashes, con
         const uint64_t len = offsets[q + 1] - offsets[q];
         records = len > SHARD_DEDUP_MAX || (opts[q].has_min_score ? opts[q].min_score : (uint32_t)((len + 19) / 20)) <= 2u;
     }
-    rc = records ? body_records() : body();
+    // (option shard_wg on every context and every rank's snapshot one its bin step would walk: the third body)
+    bool walk = !records;
+    for (uint32_t k = 0; k < n && walk; ++k) walk = ctx_opt(ss->ctxs[k], OPT_SHARD_WG) != 0 && shard_window_walk_ok(ss->locals[k]);
+    rc = records ? body_records() : walk ? body_walk() : body();
     for (uint32_t k = 0; k < n; ++k) if (shares[k]) query_batch_free(shares[k]);
     if (rc == FPX_OK && stats) {
         for (uint32_t k = 0; k < n; ++k) {
@@ -946,6 +982,11 @@ static int windows_search_batch(ShardedSnapshot* ss, const uint32_t* hashes, con
             stats->probe_kernel_ms = std::max(stats->probe_kernel_ms, t.probe_kernel_ms);
             stats->total_gpu_ms = std::max(stats->total_gpu_ms, t.total_gpu_ms);
         }
+    }
+    if (rc == FPX_OK && stats) {            // (bit 14 only when EVERY rank walked its window a query per workgroup)
+        bool all_walked = true;
+        for (uint32_t k = 0; k < n; ++k) all_walked = all_walked && (sts[k].path_flags & 16384u) != 0u;
+        if (!all_walked) stats->path_flags &= ~16384u;
     }
     {
         std::lock_guard<std::mutex> g(ss->mu);

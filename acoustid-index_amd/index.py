@@ -69,7 +69,12 @@ class Context:
         the query-per-workgroup path and sends the others through the pipeline | walks up to 8 of them one after the other a query per
         workgroup, one finish (Stats.path_flags bit 13, with bits 6 and 2; read when a snapshot is made as well: part 0 of a snapshot in
         two parts then holds all such groups) | as 1, and a batch with queries whose score floor is 1 or 2 is walked that way too where
-        'low_wg' allows it -- 1 when no group is filtered, 2 also when any is -- (bits 13 and 12 together)"""
+        'low_wg' allows it -- 1 when no group is filtered, 2 also when any is -- (bits 13 and 12 together).  'shard_wg': 0 | 1 | 2 -- a step
+        of the sharded bin protocol (shard_probe, and ShardedIndexReader over WindowShardedSegments) makes, orders and probes the keys
+        of the rank's hash window | on a rank whose snapshot is one packed, unfiltered group with its window (+ memory segments behind
+        their table) walks the window a query per workgroup and copies each query's records into its bin (Stats.path_flags bit 14,
+        with bits 4 and 6; the bins are the same, record for record) | as 1, a group with superseded docs or masked columns too;
+        values above 2 are refused"""
         check(lib().fpx_ctx_set_option(self.h, name.encode(), int(value)))
 
     def trim(self):

@@ -100,7 +100,9 @@ typedef struct {
                                    other -- k_search_query over the first, k_search_next over the others, one k_finish ("groups_wg" 1;
                                    bits 6 and 2 are set with it, and bit 8 when any of the groups is filtered).  Bits 13 and 12
                                    together ("groups_wg" 2 with "low_wg"): the batch has queries with a floor of 1 or 2 -- k_search_low
-                                   (k_search_low_filt) over the first group, k_search_low_next over the others */
+                                   (k_search_low_filt) over the first group, k_search_low_next over the others,
+                                   bit 14: a step of a sharded protocol walked its hash window a query per workgroup -- k_search_window:
+                                   no keys, each query's records copied into its bin ("shard_wg" 1 | 2; bits 4 and 6 are set with it) */
     uint64_t probe_kernel_fetched_bytes; /* block bytes the main probe kernel really fetched, in 128-byte lines: a probe
                                    whose hash the segment's presence bits know to be absent counts as a visited block (as in
                                    the reference) without the block being read, and a block that is read costs two lines up
@@ -186,6 +188,21 @@ int  fpx_ctx_device(const fpx_ctx *ctx);     /* the HIP ordinal the context live
  *                        of the one k_finish applies -- and hands over the group's top max_results: their union holds the
  *                        snapshot's.  With "low_wg" 0, or a filtered group under "low_wg" 1, such a batch is the pipeline's as
  *                        under 1; a batch without such a query runs exactly what it runs under 1
+ *   "shard_wg"           0 | 1 | 2   a step of the sharded BIN protocol (fpx_shard_probe, and fpx_sharded_search_batch on a snapshot
+ *                        sharded by hash windows) makes the keys of the rank's window, orders and probes them, and bins what the
+ *                        probe could not place (default 0) | on a rank whose snapshot is ONE packed group with its hash window and
+ *                        nothing else -- or that plus memory segments behind their one table --, unfiltered, the window is walked a
+ *                        QUERY PER WORKGROUP: k_search_window (csrc/fpx_qsearch.hpp; fpx_stats.path_flags bit 14, with bits 4 and 6)
+ *                        dedups the whole query, walks the hashes of the window and copies the query's hit records into its bin of
+ *                        8 queries with one reservation -- the bins, their counts and everything behind them (the all-to-all,
+ *                        fpx_shard_score) are as under 0, record for record.  Every other snapshot (several groups, a group in
+ *                        directory + words form, a filtered group) takes the pipeline as under 0; a query whose records outgrow
+ *                        the workgroup's array of 8192 has the same call answered by the pipeline, and the snapshot's next 32 calls
+ *                        stay there | as 1, and a group with superseded docs and/or columns outside the snapshot too, by the
+ *                        kernel's filtered form.  Values above 2 are refused.  fpx_shard_probe_keys (routed keys) has no queries
+ *                        to own and is not affected.  fpx_sharded_search_batch: with the option non-zero on its contexts and every
+ *                        device's snapshot taken by the rule above, every device gets the WHOLE batch and walks its window -- no
+ *                        keys are routed, one exchange (the bins)
  *   "fast"              1 | 0   the device-sized path (one host round trip per batch; default 1)
  *   "binned"             1 | 0   groups drop their records into bins of a few queries, scored a bin per workgroup (default 1)
  *   "rec32"              1 | 0   4-byte records in the bins where the doc ids leave room (default 1)
