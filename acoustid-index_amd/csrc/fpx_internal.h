@@ -385,6 +385,7 @@ enum CtxOpt : int {
     OPT_LOW_WG,
     OPT_GROUPS_WG,
     OPT_SHARD_WG,
+    OPT_SHARD_PACK,
     OPT_COUNT
 };
 constexpr int64_t OPT_UNSET = -2;

@@ -43,6 +43,8 @@
 // k_search_low_next over the others.
 // Option shard_wg = 1 (fpx_shard_probe, a step of the sharded bin protocol): a rank's hash-window slice of a packed group is walked by
 // k_search_window -- the same body, `SHARE` --, the query's records copied into its bin instead of counted; 2: a filtered slice too.
+// Option shard_pack = 1 (under shard_wg): that walk by k_search_packed -- `SHARE` and `PACK` --, which tests the window first and packs
+// the window's first occurrences before the rounds: a lane per probe, not per query hash (queries of up to 1024 hashes).
 // FILT (option query_wg = 2): the same for a group with superseded docs and/or columns outside the snapshot (a live index between a
 // merge and its regroup) -- every word knows its column, as in k_probe_pgroup's per-column walk: a column outside `active` gives no
 // record and no statistic, a doc of a column with a dead set is dropped after it was counted (CTR_DOCS counts before supersession).
@@ -246,10 +248,17 @@ constexpr uint32_t QS_LOW_CHUNK = 8;              // (LOW) records a lane sorts 
 // in the caller's send buffer, in bin_store's form (fpx_partition.hpp), one reservation per query.  No filter, no table, no candidates.
 constexpr uint32_t QS_SHARE_BQ = 3;               // (SHARE) queries per bin: fpx_search.hip's SHARD_BQ
 constexpr uint32_t QS_SHARE_STRIDE = 32;          // (SHARE) 32-bit words between the bins' fill counters: fpx_partition.hpp's BIN_STRIDE
-template <int NS, bool QS, bool MEM, bool FILT, bool CLS, bool LOW = false, bool NEXT = false, bool SHARE = false>
+// ... and an eighth: k_search_packed (SHARE and PACK true, below; option shard_pack) -- the window's walk with the window's PROBES packed
+// before the rounds.  A rank of N sees 1 / N of a query's hashes: under `PACK` a hash outside the window never enters the set, the first
+// occurrences inside it get dense places 0 .. m - 1 (a list in LDS, where the set was), every lane takes its hashes of the up to four
+// rounds back from there, and the rounds are ceil(m / 256), not ceil(n / 256); a wave without a probe in a round skips its walk.
+constexpr uint32_t QS_PACK_MAX = 4u * QS_WG;      // (PACK) longest query taken: what hq[] holds.  A longer one hands the step back (CTR_BINFAIL 1)
+template <int NS, bool QS, bool MEM, bool FILT, bool CLS, bool LOW = false, bool NEXT = false, bool SHARE = false, bool PACK = false>
 __device__ __forceinline__ void qs_body(const QSearchArgs& a, const GroupArgs& ga)
 {
     static_assert(!SHARE || (!QS && !CLS && !LOW && !NEXT), "a window's walk for the bin protocol: no per-query statistics, no doc classes, no sorted tail, one group");
+    static_assert(!PACK || SHARE, "packed probes: a window's walk only (without a window nearly every hash is a probe)");
+    static_assert(!PACK || 2u * QS_PACK_MAX <= QS_REC_CAP, "the packed list and its memory-table bits live at the record array's bottom");
     static_assert(!NEXT || (!CLS && !MEM), "a later group's walk: no doc classes, no memory table (they ride on the first group's launch)");
     static_assert(!(CLS && FILT), "doc classes: the unfiltered walk only");
     static_assert(!LOW || (!CLS && QS_WG == 256u && QS_REC_CAP >= 512u && (QS_REC_CAP & (QS_REC_CAP - 1u)) == 0u),
@@ -380,6 +389,14 @@ __device__ __forceinline__ void qs_body(const QSearchArgs& a, const GroupArgs& g
             return;
         }
     }
+    if constexpr (PACK) {
+        // (uniform, before the query's first barrier) a query that hq[] does not hold whole is not this kernel's: the host keeps such a
+        // batch on k_search_window -- a wrong launch hands the step back, as a query over the record array does, and stores nothing
+        if (n > QS_PACK_MAX) {
+            if (tid == 0) atomicMax(&qs_cold_args()->a.counters[CTR_BINFAIL], 1ull);
+            return;
+        }
+    }
     const uint32_t rounds = (n + QS_WG - 1u) / QS_WG, nchunks = (rounds + QS_CH - 1u) / QS_CH;
     // the query's hash set: 2^sbits >= 2 n slots
     uint32_t sbits = 8u;
@@ -388,6 +405,7 @@ __device__ __forceinline__ void qs_body(const QSearchArgs& a, const GroupArgs& g
     for (uint32_t i = tid; i < (1u << sbits); i += QS_WG) recs[i] = 0xFFFFFFFFu;
     if (tid == 0) {
         s_count = 0u; s_ntask = 0u; s_over_recs = 0u; s_seen_ones = 0u; s_ccnt = 0u; s_cshared = 0u;
+        if constexpr (PACK) s_claimed = 0u;               // (the counting passes' word, idle under SHARE: the packed probes' count)
         wg_blocks = 0; wg_docs = 0; wg_probes = 0; wg_reads = 0;
         // cancel point (src/FileSegment.zig:144), once per query, before its first probe: what ask_cancel() read
         if (c_host != 0u) { atomicExch(&qs_cold_args()->a.counters[CTR_CANCEL], 1ull); c_dev = 1ull; }
@@ -420,6 +438,8 @@ __device__ __forceinline__ void qs_body(const QSearchArgs& a, const GroupArgs& g
             const uint32_t i = (c * QS_CH + u) * QS_WG + tid;
             if (i >= n) continue;
             const uint32_t h = hc[u];
+            // (PACK) the window FIRST: another rank's hash makes no atomic and takes no slot (a duplicate of a hash of the window is in the window)
+            if constexpr (PACK) { if (h < g->win_lo || h > g->win_hi) continue; }
             bool dup;
             if (h == 0xFFFFFFFFu) dup = atomicExch(&s_seen_ones, 1u) != 0u;     // (the set's empty mark is kept apart)
             else {
@@ -439,6 +459,48 @@ __device__ __forceinline__ void qs_body(const QSearchArgs& a, const GroupArgs& g
     }
     (void)mmask;
     __syncthreads();                                    // (the set is done with: its slots are the record array now)
+    // ---- (PACK) the window's probes get DENSE places: one scan per wave on the DPP crossbar and one LDS atomic per wave (the order is
+    //      free: the bins are compared as sets), the hash to a list at the bottom of the record array -- free until the first round --,
+    //      (MEM) its memory-table bit to a second list behind it; then every lane takes its hashes of the up to four rounds back into
+    //      hq[0..3].  What indexed by the hash's RAW position -- vmask, mmask -- is remade for the packed one.
+    // (`cnt` places per lane out of `counter`, one reservation per wave: the records' below, and the packed probes')
+    auto reserve_in = [&](uint32_t* counter, uint32_t cnt) -> uint32_t {
+        const uint32_t incl = scan16(cnt);
+        const uint32_t r0 = (uint32_t)__builtin_amdgcn_readlane((int)incl, 15), r1 = (uint32_t)__builtin_amdgcn_readlane((int)incl, 31),
+                       r2 = (uint32_t)__builtin_amdgcn_readlane((int)incl, 47), r3 = (uint32_t)__builtin_amdgcn_readlane((int)incl, 63);
+        const uint32_t total = r0 + r1 + r2 + r3;
+        uint32_t wbase = 0;
+        if (total != 0u) {                                                       // (wave-uniform)
+            if (lane == 0u) wbase = atomicAdd(counter, total);
+            wbase = (uint32_t)__builtin_amdgcn_readfirstlane((int)wbase);
+        }
+        const uint32_t row = lane >> 4;
+        return wbase + (row >= 1u ? r0 : 0u) + (row >= 2u ? r1 : 0u) + (row >= 3u ? r2 : 0u) + (incl - cnt);
+    };
+    uint32_t prounds = rounds, pnchunks = nchunks;      // the rounds that are walked
+    if constexpr (PACK) {
+        uint32_t at = reserve_in(&s_claimed, (uint32_t)__popc(vmask));      // (< m <= n <= QS_PACK_MAX)
+#pragma unroll
+        for (uint32_t r = 0; r < 2u * QS_CH; ++r)
+            if (((vmask >> r) & 1u) != 0u) {
+                recs[at] = hq[r];
+                if constexpr (MEM) recs[QS_PACK_MAX + at] = (mmask >> r) & 1u;
+                ++at;
+            }
+        __syncthreads();                                // (the list is whole)
+        const uint32_t m = (uint32_t)__builtin_amdgcn_readfirstlane((int)s_claimed);
+        vmask = 0u; mmask = 0u;
+#pragma unroll
+        for (uint32_t r = 0; r < 2u * QS_CH; ++r) {
+            const uint32_t i = r * QS_WG + tid;
+            const bool has = i < m;
+            hq[r] = has ? recs[i] : 0u;
+            vmask |= (has ? 1u : 0u) << r;
+            if constexpr (MEM) mmask |= (has ? recs[QS_PACK_MAX + i] : 0u) << r;
+        }
+        prounds = (m + QS_WG - 1u) / QS_WG; pnchunks = (prounds + QS_CH - 1u) / QS_CH;
+        __syncthreads();                                // (everybody has its hashes: the array takes records now)
+    }
     QS_MARK(1);
 
     // ---- (CLS) pass `cls` of the query's ncls classes walks the query again and keeps the records of that class only: a doc's postings
@@ -475,19 +537,6 @@ __device__ __forceinline__ void qs_body(const QSearchArgs& a, const GroupArgs& g
     //      per slot: the slots are stored from the LAST down, a slot without a doc to where the nearest doc BELOW it goes -- a place of the
     //      lane's own that the doc itself, stored later, overwrites (a lane's stores to LDS keep their order); one with no doc below it, and
     //      every slot of a lane without docs, to the sink word behind the array.  The filter is counted later, over the array (every lane busy).
-    auto reserve_in = [&](uint32_t* counter, uint32_t cnt) -> uint32_t {
-        const uint32_t incl = scan16(cnt);
-        const uint32_t r0 = (uint32_t)__builtin_amdgcn_readlane((int)incl, 15), r1 = (uint32_t)__builtin_amdgcn_readlane((int)incl, 31),
-                       r2 = (uint32_t)__builtin_amdgcn_readlane((int)incl, 47), r3 = (uint32_t)__builtin_amdgcn_readlane((int)incl, 63);
-        const uint32_t total = r0 + r1 + r2 + r3;
-        uint32_t wbase = 0;
-        if (total != 0u) {                                                       // (wave-uniform)
-            if (lane == 0u) wbase = atomicAdd(counter, total);
-            wbase = (uint32_t)__builtin_amdgcn_readfirstlane((int)wbase);
-        }
-        const uint32_t row = lane >> 4;
-        return wbase + (row >= 1u ? r0 : 0u) + (row >= 2u ? r1 : 0u) + (row >= 3u ? r2 : 0u) + (incl - cnt);
-    };
     // (a round reserves its records and its tasks with ONE scan: the two counts side by side in a word -- a wave has at most 64 x 32
     // records and far fewer than 2^16 tasks --, an atomic per counter)
     auto reserve_both = [&](uint32_t cnt, uint32_t nt, uint32_t& tat) -> uint32_t {
@@ -864,15 +913,46 @@ __device__ __forceinline__ void qs_body(const QSearchArgs& a, const GroupArgs& g
         }
     };
 
+    // (PACK) the memory table's look-up for the PACKED hashes, before the rounds while hq[0..3] still hold all of them (behind the rounds
+    // the lane's registers have rolled, and a position in the batch's array no longer names the lane's hash): the look-up below, word for word
+    // -- a text of its own on purpose: one look-up with the hash's source as a parameter moved the instruction stream and the SGPR spills
+    // (30 -> 34, 42 -> 50) of every older MEM instantiation
+    auto mem_packed = [&]() {
+        if (__ballot((int)((mmask & 15u) != 0u)) == 0ull) return;                  // (wave-uniform)
+        uint32_t blo[4], bhi[4];
+#pragma unroll
+        for (uint32_t u = 0; u < 4u; ++u) {
+            const bool act = ((mmask >> u) & 1u) != 0u;
+            const uint32_t b = hq[u] >> (32u - MEMTAB_BITS);
+            blo[u] = act ? gload_u32(a.mem_bucket + b) : 0u;
+            bhi[u] = act ? gload_u32(a.mem_bucket + b + 1u) : 0u;
+        }
+#pragma unroll
+        for (uint32_t u = 0; u < 4u; ++u)
+            for (uint32_t i = blo[u]; i < bhi[u]; ++i) {
+                const uint64_t it = gload_u64(a.mem_tab + i);
+                if ((uint32_t)(it >> 32) > hq[u]) break;
+                if ((uint32_t)(it >> 32) == hq[u]) {
+                    const uint32_t at = atomicAdd(&s_count, 1u);
+                    if (at < QS_REC_CAP) recs[at] = (uint32_t)it - gmin; else s_over_recs = 1u;
+                }
+            }
+    };
+    (void)mem_packed;
+
     static_assert(QS_CH == 2, "the rounds run in pairs");
-    for (uint32_t c = 0; c < nchunks; ++c) {
+    if constexpr (MEM && PACK) mem_packed();
+    for (uint32_t c = 0; c < pnchunks; ++c) {
         if constexpr (!FILT) {
             // a round after the other, each with its 64 lines per wave under way at once (the lane's registers hold one round's)
             QS_SUB0();
             QS_ARRIVED2(hq[0], hq[1]);
             QS_SUB(7);
-            round_coop(hq[0], ((vmask >> (c * QS_CH)) & 1u) != 0u);
-            if (c * QS_CH + 1u < rounds) round_coop(hq[1], ((vmask >> (c * QS_CH + 1u)) & 1u) != 0u);      // (uniform)
+            // (PACK: the probes sit in lanes 0 .. m - 1 -- a wave whose 64 lanes hold none in a round skips that round's walk: no barrier
+            // between here and the end of the rounds, and everything in the walk is the wave's own)
+            const bool v0 = ((vmask >> (c * QS_CH)) & 1u) != 0u, v1 = ((vmask >> (c * QS_CH + 1u)) & 1u) != 0u;
+            if (!PACK || __ballot((int)v0) != 0ull) round_coop(hq[0], v0);
+            if (c * QS_CH + 1u < prounds && (!PACK || __ballot((int)v1) != 0ull)) round_coop(hq[1], v1);      // (uniform)
             QS_SUB(10);
         } else {
         // two rounds at a time, their hashes in hq[0..1]: their line heads, then -- as the heads arrive -- the words of both (and the offset
@@ -881,6 +961,7 @@ __device__ __forceinline__ void qs_body(const QSearchArgs& a, const GroupArgs& g
         QS_ARRIVED2(hq[0], hq[1]);
         QS_SUB(7);
         const bool v0 = ((vmask >> (c * QS_CH)) & 1u) != 0u, v1 = ((vmask >> (c * QS_CH + 1u)) & 1u) != 0u;
+        if (!PACK || __ballot((int)(v0 || v1)) != 0ull) {      // (PACK: a wave without a probe in the pair skips it -- wave-uniform)
         issue_heads(v0, v1);
         // (BOTH heads are under way before either is looked at: what follows sees the six words only behind this point)
         asm volatile("" : "+v"(hd[0].x), "+v"(hd[0].y), "+v"(hd[0].z), "+v"(hd[1].x), "+v"(hd[1].y), "+v"(hd[1].z));
@@ -893,7 +974,8 @@ __device__ __forceinline__ void qs_body(const QSearchArgs& a, const GroupArgs& g
         QS_ARRIVED4(gw0); QS_ARRIVED4(gw0 + 4); QS_ARRIVED4(gw0 + 8); QS_ARRIVED4(gw1); QS_ARRIVED4(gw1 + 4); QS_ARRIVED4(gw1 + 8);
         QS_SUB(9);
         probe(hq[0], hx0, hy0, v0, gw0, ov0);
-        if (c * QS_CH + 1u < rounds) probe(hq[1], hx1, hy1, v1, gw1, ov1);              // (uniform)
+        if (c * QS_CH + 1u < prounds) probe(hq[1], hx1, hy1, v1, gw1, ov1);              // (uniform)
+        }
         QS_SUB(10);
         }
         // (the window rolls: the next pair moves up, the one after it -- a query of more than 1024 hashes -- sets out)
@@ -901,13 +983,13 @@ __device__ __forceinline__ void qs_body(const QSearchArgs& a, const GroupArgs& g
         if constexpr (CLS) { if (c + 1u < nchunks) load_pair(qh, n, c + 1u, hq[0], hq[1]); }
         else {
             hq[0] = hq[2]; hq[1] = hq[3];
-            if (c + 2u < nchunks) load_pair(qh, n, c + 2u, hq[2], hq[3]);
+            if (c + 2u < pnchunks) load_pair(qh, n, c + 2u, hq[2], hq[3]);
         }
     }
     // ---- MemorySegment.search (src/MemorySegment.zig:44-54) for all memory segments at once: the query's probes looked up in the snapshot's
     //      table of their live postings -- a bit per 256 hash values says "nothing there" for nine probes in ten --, four rounds' loads out
     //      together; every matching item is a record (a doc a newer segment supersedes was dropped when the table was built)
-    if constexpr (MEM) {
+    if constexpr (MEM && !PACK) {
         for (uint32_t c0 = 0; c0 < rounds; c0 += 4u) {
             if (__ballot((int)(((mmask >> c0) & 15u) != 0u)) == 0ull) continue;          // (wave-uniform: nine probes in ten have nothing there)
             uint32_t mh[4], blo[4], bhi[4];
@@ -1610,6 +1692,17 @@ template <int NS, bool MEM, bool FILT>
 __global__ __launch_bounds__(QS_WG) FPX_QS_OCC void k_search_window(QSearchArgs a, GroupArgs ga)
 {
     qs_body<NS, false, MEM, FILT, false, false, false, true>(a, ga);
+}
+
+// k_search_packed (option shard_pack, under shard_wg): k_search_window's walk with the window's probes PACKED before the rounds (qs_body:
+// `PACK`) -- for batches whose longest query has at most QS_PACK_MAX hashes.  At N ranks a query's 1000 hashes leave 1000 / N probes:
+// k_search_window gives a lane to every HASH of a round, this one to every PROBE -- one round at 4 and 8 ranks where that one walks four,
+// three waves in four idle in it at 8.  Records, statistics, the cancel point, the queue of queries and the tail are k_search_window's.
+// The same two by-value parameters: qs_cold_args()'s layout holds.
+template <int NS, bool MEM, bool FILT>
+__global__ __launch_bounds__(QS_WG) FPX_QS_OCC void k_search_packed(QSearchArgs a, GroupArgs ga)
+{
+    qs_body<NS, false, MEM, FILT, false, false, false, true, true>(a, ga);
 }
 
 // zeroes what a batch of k_search_query adds to: the batch's counters and the statistics sets (one launch instead of two memsets)

@@ -838,6 +838,16 @@ static void launch_search_window(bool ns8, bool mem, bool filt, dim3 grid, hipSt
 #undef FPX_LW_FILT
 #undef FPX_LW
 }
+// ... and k_search_packed's (the same slice with the window's probes packed before the rounds: option shard_pack under shard_wg)
+static void launch_search_packed(bool ns8, bool mem, bool filt, dim3 grid, hipStream_t st, const QSearchArgs& qa, const GroupArgs& g)
+{
+#define FPX_LP(NS, MEM, FILT) hipLaunchKernelGGL((k_search_packed<NS, MEM, FILT>), grid, dim3(QS_WG), QS_LDS_BYTES, st, qa, g)
+#define FPX_LP_FILT(NS, MEM) do { if (filt) FPX_LP(NS, MEM, true); else FPX_LP(NS, MEM, false); } while (0)
+    if (ns8) { if (mem) FPX_LP_FILT(8, true); else FPX_LP_FILT(8, false); }
+    else { if (mem) FPX_LP_FILT(16, true); else FPX_LP_FILT(16, false); }
+#undef FPX_LP_FILT
+#undef FPX_LP
+}
 // a query-per-workgroup path opens: the queries' candidate slots (`extra_words` of the caller's behind them), the counters and statistics
 // sets zeroed, the probe's first event -- and the arguments every such kernel takes, from the batch (Args: QFrameArgs | QSearchArgs,
 // by their same-named members; which queries a launch takes is the caller's to say)
@@ -2225,6 +2235,7 @@ static unsigned shard_sort_bits(unsigned win_bits) { return win_bits >= 8u ? 0u 
 
 static_assert(SHARD_DEDUP_MAX == DEDUP_MAX, "fpx_sharded.hip routes longer queries to the record protocol");
 static_assert(QS_SHARE_BQ == SHARD_BQ && QS_SHARE_STRIDE == BIN_STRIDE && DEDUP_MAX <= QS_MAX_HASHES, "k_search_window fills the protocol's bins");
+static_assert(QS_PACK_MAX <= DEDUP_MAX, "k_search_packed takes the shorter queries of what k_search_window takes");
 // Option shard_wg: would a step of the bin protocol on this snapshot WALK ITS WINDOW A QUERY PER WORKGROUP (k_search_window, fpx_qsearch.hpp)?
 // ONE packed group with its hash window and nothing else -- or that plus memory segments behind their one table --, unfiltered (1) or
 // filtered too (2).  (The caller has refused solo and block segments and memory segments without a table.)  The back-off after a
@@ -2310,7 +2321,10 @@ int shard_probe_impl(Snapshot* snap, const QueryBatch* qb, uint32_t world, uint3
         uint64_t rec_cap = cell_cap;                           // records a bin's cells hold
         // option shard_wg: the window walked a query per workgroup (k_search_window) -- no keys, one launch.  After a hand-back the
         // snapshot's next 32 calls do not try (qs_skip, as on one GPU)
-        bool walk = shard_window_walk_ok(snap), walked = false;
+        // option shard_pack: the walk by k_search_packed -- the window's probes packed before the rounds -- for a batch whose longest query
+        // its hash registers hold whole; a longer one keeps the batch on k_search_window
+        bool walk = shard_window_walk_ok(snap), walked = false, packed = false;
+        const bool pack = ctx_opt(snap->ctx, OPT_SHARD_PACK) == 1 && max_len <= QS_PACK_MAX;
         if (walk) {
             const uint32_t skip = __atomic_load_n(&snap->qs_skip, __ATOMIC_RELAXED);
             if (skip != 0u) { __atomic_store_n(&snap->qs_skip, skip - 1u, __ATOMIC_RELAXED); walk = false; }
@@ -2334,7 +2348,8 @@ int shard_probe_impl(Snapshot* snap, const QueryBatch* qb, uint32_t world, uint3
                 const GroupArgs gargs{snap->h_group[0], snap->d_direct};
                 const dim3 grid(std::min<uint32_t>(B, (uint32_t)device_cus(snap->ctx) * QS_WGS_PER_CU));
                 FPX_HIP(hipEventRecord(ws->ev_probe0, st));
-                launch_search_window(snap->groups[0]->ns == 8u, qa.mem_tab != nullptr, group_filtered(snap->h_group[0]), grid, st, qa, gargs);
+                if (pack) launch_search_packed(snap->groups[0]->ns == 8u, qa.mem_tab != nullptr, group_filtered(snap->h_group[0]), grid, st, qa, gargs);
+                else launch_search_window(snap->groups[0]->ns == 8u, qa.mem_tab != nullptr, group_filtered(snap->h_group[0]), grid, st, qa, gargs);
                 FPX_HIP(hipEventRecord(ws->ev_probe1, st));
                 hipLaunchKernelGGL(k_cell_counts, dim3((ncells + 255) / 256), dim3(256), 0, st, (const unsigned int*)ws->d_cells, ncells, d_send_counts, ws->d_counters,
                                    rec32 << 31);
@@ -2353,7 +2368,7 @@ int shard_probe_impl(Snapshot* snap, const QueryBatch* qb, uint32_t world, uint3
                     walk = false; attempt = -1;
                     continue;
                 }
-                walked = true;
+                walked = true; packed = pack;
                 break;
             }
             const uint64_t P = (uint64_t)B * stride;
@@ -2455,6 +2470,7 @@ int shard_probe_impl(Snapshot* snap, const QueryBatch* qb, uint32_t world, uint3
                 stats->hits = s.records;
                 stats->probe_kernel_fetched_bytes = (dreads + 1) / 2 * 128ull;
                 stats->path_flags |= 64u | 16384u;
+                if (packed) stats->path_flags |= 32768u;      // (bit 15: k_search_packed answered the call)
             }
         }
         return FPX_OK;

@@ -987,6 +987,10 @@ static int windows_search_batch(ShardedSnapshot* ss, const uint32_t* hashes, con
         bool all_walked = true;
         for (uint32_t k = 0; k < n; ++k) all_walked = all_walked && (sts[k].path_flags & 16384u) != 0u;
         if (!all_walked) stats->path_flags &= ~16384u;
+        // (... and bit 15 only when every rank's walk was k_search_packed's: option shard_pack on every context)
+        bool all_packed = true;
+        for (uint32_t k = 0; k < n; ++k) all_packed = all_packed && (sts[k].path_flags & 32768u) != 0u;
+        if (!all_packed) stats->path_flags &= ~32768u;
     }
     {
         std::lock_guard<std::mutex> g(ss->mu);

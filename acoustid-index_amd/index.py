@@ -74,7 +74,10 @@ class Context:
         of the rank's hash window | on a rank whose snapshot is one packed, unfiltered group with its window (+ memory segments behind
         their table) walks the window a query per workgroup and copies each query's records into its bin (Stats.path_flags bit 14,
         with bits 4 and 6; the bins are the same, record for record) | as 1, a group with superseded docs or masked columns too;
-        values above 2 are refused"""
+        values above 2 are refused.  'shard_pack': 0 | 1 -- a step that 'shard_wg' lets walk its window gives a lane to every query hash
+        of a round | packs the window's first occurrences before the rounds, a lane per probe, where the batch's longest query has at
+        most 1024 hashes (Stats.path_flags bit 15, with bits 14, 6 and 4; the bins are the same, record for record); values above 1
+        are refused, and without 'shard_wg' it does nothing"""
         check(lib().fpx_ctx_set_option(self.h, name.encode(), int(value)))
 
     def trim(self):

@@ -102,7 +102,9 @@ typedef struct {
                                    together ("groups_wg" 2 with "low_wg"): the batch has queries with a floor of 1 or 2 -- k_search_low
                                    (k_search_low_filt) over the first group, k_search_low_next over the others,
                                    bit 14: a step of a sharded protocol walked its hash window a query per workgroup -- k_search_window:
-                                   no keys, each query's records copied into its bin ("shard_wg" 1 | 2; bits 4 and 6 are set with it) */
+                                   no keys, each query's records copied into its bin ("shard_wg" 1 | 2; bits 4 and 6 are set with it),
+                                   bit 15: that walk was k_search_packed's -- the window's probes packed before the rounds ("shard_pack" 1
+                                   under "shard_wg"; bits 14, 6 and 4 are set with it).  fpx_sharded_search_batch: when every device's was */
     uint64_t probe_kernel_fetched_bytes; /* block bytes the main probe kernel really fetched, in 128-byte lines: a probe
                                    whose hash the segment's presence bits know to be absent counts as a visited block (as in
                                    the reference) without the block being read, and a block that is read costs two lines up
@@ -203,6 +205,15 @@ int  fpx_ctx_device(const fpx_ctx *ctx);     /* the HIP ordinal the context live
  *                        to own and is not affected.  fpx_sharded_search_batch: with the option non-zero on its contexts and every
  *                        device's snapshot taken by the rule above, every device gets the WHOLE batch and walks its window -- no
  *                        keys are routed, one exchange (the bins)
+ *   "shard_pack"         0 | 1   a step that "shard_wg" lets walk its window does so by k_search_window: every one of a query's hashes
+ *                        goes through the dedup set and gets a lane in ceil(hashes / 256) rounds, the window test behind (default
+ *                        0) | by k_search_packed (csrc/fpx_qsearch.hpp; fpx_stats.path_flags bit 15, with bits 14, 6 and 4): the window
+ *                        test comes FIRST, the window's first occurrences are packed into dense places before the rounds -- a lane
+ *                        per PROBE, ceil(probes / 256) rounds, a wave without a probe skipping its round -- for a batch whose
+ *                        longest query has at most 1024 hashes; a batch with a longer one (fpx_shard_probe takes up to 2048) runs
+ *                        k_search_window as under 0.  The bins, their counts and the statistics are the same, record for record; the
+ *                        hand-back to the pipeline and its back-off are "shard_wg"'s.  Values above 1 are refused.  Without
+ *                        "shard_wg" the option does nothing
  *   "fast"              1 | 0   the device-sized path (one host round trip per batch; default 1)
  *   "binned"             1 | 0   groups drop their records into bins of a few queries, scored a bin per workgroup (default 1)
  *   "rec32"              1 | 0   4-byte records in the bins where the doc ids leave room (default 1)
