@@ -428,6 +428,7 @@ static const OptInfo OPT_TABLE[OPT_COUNT] = {
     /* OPT_GROUPS_WG */          {"groups_wg", "FPX_GROUPS_WG", 0, 0, false},                    // 0 | 1 | 2: a snapshot of SEVERAL packed groups keeps the largest for k_search_query and sends the others through the pipeline | walks up to QS_MAX_GROUPS of them one after the other a query per workgroup (k_search_next, fpx_qsearch.hpp; read per batch, and when a snapshot's two parts are made) | as 1, a batch with queries whose floor is 1 or 2 too where low_wg allows it (1: no group filtered, 2: any; k_search_low / k_search_low_filt over the first group, k_search_low_next over the others)
     /* OPT_SHARD_WG */           {"shard_wg", "FPX_SHARD_WG", 0, 0, false},                      // 0 | 1 | 2: a step of the sharded bin protocol (fpx_shard_probe) on a rank whose snapshot is ONE packed group with its hash window (+ memory segments behind their table) makes and orders the window's keys and probes them (the pipeline) | walks the window a query per workgroup and copies each query's records into its bin (k_search_window, fpx_qsearch.hpp; unfiltered) | as 1, a group with superseded docs or masked columns too
     /* OPT_SHARD_PACK */         {"shard_pack", "FPX_SHARD_PACK", 0, 0, false},                  // 0 | 1: a step that shard_wg lets walk its window does so by k_search_window, a lane per query HASH and round | by k_search_packed, which packs the window's first occurrences before the rounds -- a lane per PROBE -- where the batch's longest query has at most 1024 hashes (fpx_qsearch.hpp; a longer one keeps the batch on k_search_window).  Nothing without shard_wg
+    /* OPT_FILT_COOP */          {"filt_coop", "FPX_FILT_COOP", 0, 0, false},                    // 0 | 1: ONE packed group with superseded docs or masked columns, under query_wg 2, is searched by k_search_query's filtered form (the per-lane walk) | by k_search_filt -- eight lanes to a line behind the group's union dead-set bitmap (fpx_qsearch.hpp) -- where the snapshot, made under 1, holds that bitmap or the group has no dead set.  Read when a snapshot is made (the bitmap) and per batch (the kernel)
 };
 
 int64_t ctx_opt(const Ctx* c, CtxOpt o)
@@ -672,6 +673,7 @@ int fpx_ctx_set_option(fpx_ctx* ctx, const char* name, int64_t value)
     }
     if (o == OPT_SHARD_WG && value > 2) { set_error("fpx_ctx_set_option: shard_wg is 0, 1 or 2"); return FPX_E_INVAL; }
     if (o == OPT_SHARD_PACK && value > 1) { set_error("fpx_ctx_set_option: shard_pack is 0 or 1"); return FPX_E_INVAL; }
+    if (o == OPT_FILT_COOP && value > 1) { set_error("fpx_ctx_set_option: filt_coop is 0 or 1"); return FPX_E_INVAL; }
     // below the option's smallest value: back to the fallback (environment variable, then default)
     c->opts[o].store(value < OPT_TABLE[o].min_set ? OPT_UNSET : value, std::memory_order_relaxed);
     return FPX_OK;
@@ -1111,6 +1113,12 @@ int fpx_snapshot_create(fpx_ctx* ctx_, fpx_segment* const* segs, uint32_t num_se
             }
         }
     }
+    // Option filt_coop = 1 -- the value in force now --: the snapshot that is searched as ONE packed group (this one, or its part 0) gets
+    // the group's union dead-set bitmap, k_search_filt's first test (fpx_qsearch.hpp).  Without one the filtered form stays the per-lane walk.
+    if (ctx_opt(c, OPT_FILT_COOP) == 1) {
+        const int urc = build_dead_union(sn->part[0] ? sn->part[0] : sn);
+        if (urc != FPX_OK) { snapshot_free(sn); return urc; }
+    }
     *out = reinterpret_cast<fpx_snapshot*>(sn);
     return FPX_OK;
 }
@@ -1222,7 +1230,11 @@ static int snapshot_build(Ctx* c, fpx_segment* const* segs, uint32_t num_segs, c
             d.num_blocks = s->num_blocks; d.block_size = s->block_size; d.bucket_shift = s->bucket_shift;
             d.min_doc_id = s->min_doc_id; d.num_dead = (uint32_t)dead.size(); d.shadow_lo = slo; d.shadow_hi = shi;
             d.drec = s->d_drec; d.primary = s->d_primary; d.extras = s->d_extras; d.first_hash = s->first_hash; d.last_hash = s->last_hash; d.extras_shift = s->extras_shift;
-            if (s->direct) { sn->h_direct.push_back(d); direct_segs.push_back(s); continue; }   // searched by k_probe_group / k_probe_direct alone
+            if (s->direct) {
+                sn->h_direct.push_back(d); direct_segs.push_back(s);
+                sn->direct_dead.push_back(dead.empty() ? nullptr : sn->dead_sets.back()); sn->direct_max_doc.push_back(s->max_doc_id);
+                continue;
+            }   // searched by k_probe_group / k_probe_direct alone
             sn->h_file.push_back(d);
             sn->max_block_size = std::max(sn->max_block_size, s->block_size);
             if (s->block_size != 512) sn->all_512 = false;
@@ -1339,6 +1351,9 @@ int fpx_snapshot_info(const fpx_snapshot* snap, uint64_t* info, uint32_t n)
         if (s->kind == 0 && s->settled) settled += 1;
         bytes += fpx_segment_device_bytes(reinterpret_cast<const fpx_segment*>(s));
     }
+    // slot 12: the bytes of the union dead-set bitmap that k_search_filt tests first (the snapshot's own, or its part 0's; 0: none)
+    const Snapshot* us = sn->part[0] ? sn->part[0] : sn;
+    if (n > 12u) info[12] = us->dead_union ? us->dead_union->words * 4ull : 0ull;
     const uint64_t v[12] = {sn->n_lean, sn->n_gen, sn->n_small, sn->n_solo, grouped, sn->n_group, packed, sn->n_mem, settled, bytes,
                             // a batch of this snapshot takes the one-launch path (records binned by the probe kernel, scored a bin per workgroup) when it
                             // holds groups and nothing else

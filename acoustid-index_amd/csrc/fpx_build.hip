@@ -1531,4 +1531,63 @@ int segment_merge_device(Ctx* ctx, const std::vector<MergeSource>& srcs, uint32_
     return encode_sorted_items(items, n_live, min_doc_id, block_size, s, st);
 }
 
+// ---- the union dead-set bitmap of a packed group within a snapshot (DeadUnion; k_search_filt's first test, fpx_qsearch.hpp)
+// one column's sorted list into the bitmap: bit id - gmin, an id outside [gmin, gmin + 32 words - 1] sets nothing
+__global__ __launch_bounds__(256) void k_dead_union(const uint32_t* __restrict__ list, uint32_t n, uint32_t gmin, uint64_t words, uint32_t* __restrict__ bits)
+{
+    for (uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (uint64_t)gridDim.x * blockDim.x) {
+        const uint32_t rel = list[i] - gmin;               // (an id below gmin wraps to a large value: refused by the test below)
+        if ((uint64_t)(rel >> 5) < words) atomicOr(&bits[rel >> 5], 1u << (rel & 31u));
+    }
+}
+
+int build_dead_union(Snapshot* sn)
+{
+    if (sn->n_group != 1u || !sn->groups[0]->packed || sn->h_group[0].any_dead == 0u) return FPX_OK;
+    Group* g = sn->groups[0].get();
+    const GroupDesc& gd = sn->h_group[0];
+    // the range: [gmin, the largest doc id of the group's active columns]; wider than 2^29 ids: no bitmap (the limit of a column's own)
+    auto du = std::make_shared<DeadUnion>();
+    du->device = sn->ctx->device; du->active = gd.active;
+    uint32_t max_doc = gd.gmin;
+    for (uint32_t s = 0; s < FUSE_MAX; ++s) {
+        if (((gd.active >> s) & 1u) == 0u) continue;
+        const uint32_t i = gd.seg_index[s];
+        if (i >= sn->direct_dead.size()) return FPX_OK;
+        du->sets[s] = sn->direct_dead[i];
+        max_doc = std::max(max_doc, sn->direct_max_doc[i]);
+    }
+    if ((uint64_t)max_doc - gd.gmin >= (1ull << 29)) return FPX_OK;
+    du->words = ((uint64_t)(max_doc - gd.gmin) >> 5) + 1u;
+    {
+        // the same group, the same columns, the same DeadSet objects as the group's last bitmap: that one (nothing is allocated)
+        std::lock_guard<std::mutex> lk(g->union_mu);
+        if (std::shared_ptr<DeadUnion> last = g->last_union.lock()) {
+            bool same = last->device == du->device && last->active == du->active && last->words == du->words;
+            for (uint32_t s = 0; s < FUSE_MAX && same; ++s) same = last->sets[s] == du->sets[s];
+            if (same) { sn->dead_union = last; return FPX_OK; }
+        }
+    }
+    FPX_HIP(hipSetDevice(du->device));
+    hipStream_t st = 0;
+    if (dmalloc(&du->d_bits, du->words * sizeof(uint32_t)) != hipSuccess) { (void)hipGetLastError(); du->d_bits = nullptr; return FPX_OK; }
+    // (zero first: fresh memory holds anything)
+    FPX_HIP(hipMemsetAsync(du->d_bits, 0, du->words * sizeof(uint32_t), st));
+    for (uint32_t s = 0; s < FUSE_MAX; ++s) {
+        const DeadSet* ds = du->sets[s].get();
+        if (!ds || ds->ids.empty() || !ds->d_list) continue;
+        const uint32_t n = (uint32_t)ds->ids.size();
+        hipLaunchKernelGGL(k_dead_union, dim3(std::min<uint32_t>((n + 255u) / 256u, 1024u)), dim3(256), 0, st,
+                           (const uint32_t*)ds->d_list, n, gd.gmin, du->words, du->d_bits);
+    }
+    FPX_HIP(hipGetLastError());
+    FPX_HIP(hipStreamSynchronize(st));
+    {
+        std::lock_guard<std::mutex> lk(g->union_mu);
+        g->last_union = du;
+    }
+    sn->dead_union = du;
+    return FPX_OK;
+}
+
 }  // namespace fpx

@@ -165,6 +165,23 @@ struct DeadSet {
     }
 };
 
+// The UNION of the dead sets of a packed group's columns within one snapshot, as a bitmap in HBM over the group's doc range: bit d - gmin
+// is set iff some column of the group that belongs to the snapshot has d in its dead set (k_search_filt's first test, fpx_qsearch.hpp;
+// option filt_coop).  Built on the device from the columns' lists (build_dead_union, fpx_build.hip).  Owned by the snapshots that hold it:
+// the group remembers the latest one weakly, and the next snapshot of the same group whose columns carry the SAME DeadSet objects shares
+// it -- DeadSet's own pattern one level up: a publish that changes no dead set allocates nothing.
+struct DeadUnion {
+    int device = 0;
+    uint32_t* d_bits = nullptr;
+    uint64_t words = 0;                                    // 32-bit words: (max doc id of the active columns - gmin) / 32 + 1
+    uint32_t active = 0;                                   // the columns it was made over ...
+    std::shared_ptr<DeadSet> sets[16];                     // ... and the dead set of each (null: none) -- held, so that "the same object" stays decidable
+    ~DeadUnion()
+    {
+        if (d_bits) { (void)hipSetDevice(device); (void)hipFree(d_bits); }
+    }
+};
+
 // The per-segment direct-addressed arrays (fpx_direct.hpp).  Snapshots that probe the segment on its own (k_probe_direct) keep
 // them alive; a segment that joins a group lets go of its reference.
 struct DirectStore {
@@ -224,6 +241,7 @@ struct Group {
     uint32_t* chunk_alloc(size_t bytes);   // null: out of memory
     uint32_t** d_ext_tab = nullptr;        // the same addresses in device memory (GroupDesc::ext_tab)
     uint32_t min_doc[FUSE_MAX] = {}, first_hash[FUSE_MAX] = {}, last_hash[FUSE_MAX] = {};
+    std::mutex union_mu; std::weak_ptr<DeadUnion> last_union;      // the union dead-set bitmap of the latest snapshot that made one over this group
     uint64_t device_bytes = 0, total_words = 0, total_list_words = 0, doubles = 0, overflow_lines = 0, overflow_words = 0;
     ~Group();
 };
@@ -298,6 +316,9 @@ struct Snapshot {
     uint32_t* d_membits = nullptr;         // one bit per 256 hash values: the table holds a posting there (k_probe_memtab's first load)
     uint64_t mem_items = 0;                // items of all memory segments together (0: nothing to look up, table or not)
     std::vector<std::shared_ptr<DeadSet>> dead_sets;   // shared with the segments' caches
+    std::vector<std::shared_ptr<DeadSet>> direct_dead; // parallel to h_direct: the segment's dead set here, or null
+    std::vector<uint32_t> direct_max_doc;              // parallel to h_direct: the segment's largest doc id
+    std::shared_ptr<DeadUnion> dead_union;             // of its ONE packed group (made under option filt_coop = 1: fpx_snapshot_create), or null
     uint32_t max_block_size = 0;
     bool all_512 = true;                 // every file segment uses 512-B blocks (the only size the reference writes)
 };
@@ -386,6 +407,7 @@ enum CtxOpt : int {
     OPT_GROUPS_WG,
     OPT_SHARD_WG,
     OPT_SHARD_PACK,
+    OPT_FILT_COOP,
     OPT_COUNT
 };
 constexpr int64_t OPT_UNSET = -2;
@@ -535,6 +557,9 @@ int segment_build_impl(Ctx* ctx, const uint64_t* items_host, uint64_t n, bool so
                        uint32_t min_doc_id, uint32_t max_doc_id, uint64_t commit_id, Segment* s);
 // exclusive scan of n 32-bit counts into 64-bit offsets (+ their total), one workgroup
 int scan_counts_u32(const uint32_t* counts, uint64_t n, uint64_t* offsets, uint64_t* total, hipStream_t st);
+// the union dead-set bitmap of the snapshot's one packed group (Snapshot::dead_union): shared with the group's last one or built on the
+// device.  Leaves it null -- and returns FPX_OK -- where there is nothing to build, the id range is wider than 2^29, or memory is short
+int build_dead_union(Snapshot* sn);
 int decode_small_segment(Segment* s);     // fills d_small_items / d_bstart of a resident file segment
 int build_presence(Segment* s);           // fills d_blockrec and d_proberec (both required by the lean kernel) of a resident file segment
 struct HashRange { uint32_t lo, hi, rec0, whole; };      // hashes [lo, hi] into records counted from rec0; whole: the blocks are the whole segment

@@ -26,7 +26,8 @@
 // and the per-hash statistics once; what the group needs of it goes back ready-made -- two words indexed by the LINE's word number: which
 // words are the hash's, which of them second words of doubles; and, before the loads, the line's number in the group --, and every lane
 // classifies its own four words of each line where they landed: every inline word is walked, only lists and words in `ext` are tasks.
-// The filtered form keeps the per-lane walk (a word's column is bookkeeping of its own).
+// The filtered form keeps the per-lane walk (a word's column is bookkeeping of its own) -- but for k_search_filt (`COOP`, option
+// filt_coop = 1): the same rounds for a filtered group, a word's column looked for only where the group's union dead-set bitmap says so.
 //
 // Taken by run_batch for snapshots that are ONE packed group and nothing else (the resident index between merges), every column searched,
 // no superseded docs, queries of up to QS_MAX_HASHES hashes with a floor above 2; a query whose records outgrow the LDS array (hot
@@ -124,6 +125,9 @@ struct QSearchArgs {
     // it every other kernel's argument offsets, stays as it is: cands = the bins ([bin][cand_cap] records, 4 or 8 bytes each), cand_cap = a
     // bin's capacity in RECORDS, qcand_n = the bins' fill counters (BIN_STRIDE words apart), redo_cap = 1: 4-byte records (bin_record32),
     // 0: 8-byte ones; qcand and redo are null.
+    // k_search_filt (FILT and COOP) has no redo list either -- hot_wg is unfiltered-only -- and CARRIES THE GROUP'S UNION DEAD-SET BITMAP there, on
+    // the same terms: redo = the bitmap's words (32-bit, bit doc - gmin; Snapshot::dead_union) or null where no column has a dead set,
+    // redo_cap = the number of its LAST word (a word beyond it is not read).
 };
 
 // The kernel's arguments as its two by-value parameters lay them out in the kernel-argument segment.  Most of them are needed once per
@@ -253,9 +257,10 @@ constexpr uint32_t QS_SHARE_STRIDE = 32;          // (SHARE) 32-bit words betwee
 // occurrences inside it get dense places 0 .. m - 1 (a list in LDS, where the set was), every lane takes its hashes of the up to four
 // rounds back from there, and the rounds are ceil(m / 256), not ceil(n / 256); a wave without a probe in a round skips its walk.
 constexpr uint32_t QS_PACK_MAX = 4u * QS_WG;      // (PACK) longest query taken: what hq[] holds.  A longer one hands the step back (CTR_BINFAIL 1)
-template <int NS, bool QS, bool MEM, bool FILT, bool CLS, bool LOW = false, bool NEXT = false, bool SHARE = false, bool PACK = false>
+template <int NS, bool QS, bool MEM, bool FILT, bool CLS, bool LOW = false, bool NEXT = false, bool SHARE = false, bool PACK = false, bool COOP = false>
 __device__ __forceinline__ void qs_body(const QSearchArgs& a, const GroupArgs& ga)
 {
+    static_assert(!COOP || (FILT && !CLS && !LOW && !NEXT && !SHARE), "the filtered walk eight lanes to a line: k_search_filt only");
     static_assert(!SHARE || (!QS && !CLS && !LOW && !NEXT), "a window's walk for the bin protocol: no per-query statistics, no doc classes, no sorted tail, one group");
     static_assert(!PACK || SHARE, "packed probes: a window's walk only (without a window nearly every hash is a probe)");
     static_assert(!PACK || 2u * QS_PACK_MAX <= QS_REC_CAP, "the packed list and its memory-table bits live at the record array's bottom");
@@ -345,7 +350,11 @@ __device__ __forceinline__ void qs_body(const QSearchArgs& a, const GroupArgs& g
     auto line_of = [&](uint32_t h) -> const uint32_t* { return g->lines + (size_t)((h >> HVL) - g->line0) * GROUP_LINE_WORDS; };
     // (the lane's hashes of pair c of a query of n_ hashes at qh_)
     auto load_pair = [&](const uint32_t* qh_, uint32_t n_, uint32_t c, uint32_t& h0, uint32_t& h1) {
-        const uint32_t i = c * QS_CH * QS_WG + tid;
+        // ((COOP) the lane's number is taken afresh: held across the kernel, tid + 512 and tid + 768 -- the second pair's places -- were the
+        // registers k_search_filt<16, ..> did not have, and went to scratch)
+        uint32_t t = tid;
+        if constexpr (COOP) asm volatile("" : "+v"(t));
+        const uint32_t i = c * QS_CH * QS_WG + t;
         h0 = i < n_ ? gload_u32(qh_ + i) : 0u;
         h1 = i + QS_WG < n_ ? gload_u32(qh_ + i + QS_WG) : 0u;
     };
@@ -532,6 +541,17 @@ __device__ __forceinline__ void qs_body(const QSearchArgs& a, const GroupArgs& g
         const uint32_t di = s_dseg[s];
         return di != 0xFFFFFFFFu && is_dead_seg(ga.segs[di], doc);
     };
+    // (COOP) the group's UNION dead-set bitmap of this snapshot -- bit doc - gmin: some column's dead set holds the doc --, words 0 .. ub_last,
+    // or null: no column has a dead set.  In QSearchArgs::redo / redo_cap, which the filtered form has no other use for.  A doc whose bit is
+    // clear is live whatever its column; one whose bit is set asks its own column's set (dead_in)
+    const uint32_t* ub = nullptr;
+    uint32_t ub_last = 0u;
+    if constexpr (COOP) { ub = reinterpret_cast<const uint32_t*>(a.redo); ub_last = a.redo_cap; }
+    auto union_hit = [&](uint32_t rel) -> bool {            // (rel: doc - gmin, what a word holds)
+        const uint32_t i = rel >> 5;
+        return ub != nullptr && i <= ub_last && ((gload_u32(ub + i) >> (rel & 31u)) & 1u) != 0u;
+    };
+    (void)ub; (void)ub_last; (void)union_hit;
     // ---- records.  `n` docs of the lane (mask km over d[]) join the query's array: one reservation per wave -- a scan on the DPP
     //      crossbar: the whole wave is here (fpx_pgroup.hpp x5) --, doc j at pos + (docs of the lane before it).  No branch and no select
     //      per slot: the slots are stored from the LAST down, a slot without a doc to where the nearest doc BELOW it goes -- a place of the
@@ -833,6 +853,19 @@ __device__ __forceinline__ void qs_body(const QSearchArgs& a, const GroupArgs& g
         const uint32_t wb = (start + 3u) & 31u;
         uint32_t wr = ((1u << in_line) - 1u) << wb;
         uint32_t ws = second << wb;
+        // (FILT) a word of a column outside the snapshot is not the hash's: never kept, never a list, never counted -- the hash's lane
+        // walks its columns once (probe's amask, over the words in the line) where any of them is masked
+        if constexpr (FILT) {
+            if ((pm & ~active) != 0u) {
+                uint32_t am = 0u;
+                for (uint32_t r = pm, i = 0, w = 0; r != 0u && w < in_line; r &= r - 1u, ++i) {
+                    const uint32_t s = (uint32_t)__builtin_ctz(r), span = 1u + ((dm >> i) & 1u);
+                    am |= ((active >> s) & 1u) != 0u ? ((1u << span) - 1u) << w : 0u;
+                    w += span;
+                }
+                wr &= am << wb;
+            }
+        }
         uint32_t rm32 = 0, sec32 = 0;                    // the lane's words (register 4 k + t) that belong to their line's hash; second words among them
         const uint32_t nb = 4u * sub;
         // (four lines at a time -- eight broadcasts, one wait --: sixteen broadcasts at once cost sixteen registers)
@@ -856,7 +889,7 @@ __device__ __forceinline__ void qs_body(const QSearchArgs& a, const GroupArgs& g
         my_docs += nrec;
         my_blocks += (uint32_t)__popc(keep & ~sec32);
         // (CLS) what the walk SAW is counted above, whatever the class; the records are this pass's class only
-        const uint32_t kept = keep & cm32;
+        uint32_t kept = keep & cm32;
         if constexpr (CLS) nrec = (uint32_t)__popc(kept);
         // (the scan histograms: a double is ONE observation of two docs, counted where its second word is -- the upper half of my_probes)
         if constexpr (SCAN_HIST && (FPX_SH_BITS & 2)) my_probes += (uint32_t)__popc(keep & sec32) << 16;
@@ -872,6 +905,58 @@ __device__ __forceinline__ void qs_body(const QSearchArgs& a, const GroupArgs& g
             const uint32_t lo = (j0 & 1u) ? w1 : w0, hi = (j0 & 1u) ? w3 : w2;
             return (j0 & 2u) ? hi : lo;
         };
+        // (FILT) what the word's lane needs of its line's hash to name the word's column: pm | dm << 16 and start, from the hash's lane
+        // -- number j0 >> 2 of the group --, next to the chunk.  The whole wave is here.  -> the column of the lane's register j0
+        const uint32_t pmdm = pm | (dm << 16);
+        (void)pmdm;
+        auto col_of = [&](uint32_t j0, bool want) -> uint32_t {
+            const int src = (int)((lane & 56u) | (j0 >> 2));
+            const uint32_t pd = (uint32_t)__shfl((int)pmdm, src), st = (uint32_t)__shfl((int)start, src);
+            return want ? qs_word_cols(pd & 0xFFFFu, pd >> 16, nb + (j0 & 3u) - 3u - st, 1u) : 0u;
+        };
+        (void)col_of;
+        // (FILT) supersession, behind the counting above (CTR_DOCS counts before it): every kept doc word against the UNION bitmap, eight
+        // loads of a lane under way together and no column needed; only a word whose bit is set -- hardly any: noted in hit32, taken up
+        // behind the loop -- finds its column and runs the exact test.  A null bitmap: no column has a dead set, nothing to test.
+        if constexpr (FILT) {
+            if (ub != nullptr) {                                                   // (uniform)
+                uint32_t left = keep, hit32 = 0u;                                  // hit32: the lane's registers whose union bit is set
+                while (__ballot((int)(left != 0u)) != 0ull) {
+                    // (a word's place in its bitmap word waits for the load packed, eight bits each: the word itself does not stay live)
+                    uint32_t bv[8], it = left, shp[2] = {0u, 0u}, inm = 0u;
+#pragma unroll
+                    for (uint32_t u = 0; u < 8u; ++u) {
+                        const bool has = it != 0u;
+                        const uint32_t w = word_at(has ? (uint32_t)__builtin_ctz(it) : 0u);
+                        it &= it - 1u;
+                        // (a lane without an eighth word reads the bitmap's first: one address, a hit, no load under a branch)
+                        const bool in = has && (w >> 5) <= ub_last;
+                        bv[u] = gload_u32(reinterpret_cast<const uint32_t*>(reinterpret_cast<const uint8_t*>(ub) + (in ? (w >> 5) << 2 : 0u)));
+                        shp[u >> 2] |= (w & 31u) << (8u * (u & 3u));
+                        inm |= (in ? 1u : 0u) << u;
+                        asm volatile("" : "+v"(shp[u >> 2]), "+v"(inm));
+                    }
+                    uint32_t hm = 0u;
+#pragma unroll
+                    for (uint32_t u = 0; u < 8u; ++u) hm |= ((bv[u] >> ((shp[u >> 2] >> (8u * (u & 3u))) & 31u)) & 1u) << u;
+                    hm &= inm;
+                    if (hm != 0u) {                                                // (rare, and the lane's own business: which registers those were)
+                        uint32_t jt = left;
+                        for (uint32_t u = 0; u < 8u && jt != 0u; ++u, jt &= jt - 1u) hit32 |= ((hm >> u) & 1u) << (uint32_t)__builtin_ctz(jt);
+                    }
+                    left = it;
+                }
+                // (rare: a superseded doc, or its live rewrite -- the wave makes a turn per such word of its fullest lane)
+                while (__ballot((int)(hit32 != 0u)) != 0ull) {
+                    const bool hit = hit32 != 0u;
+                    const uint32_t j0 = hit ? (uint32_t)__builtin_ctz(hit32) : 0u;
+                    hit32 &= hit32 - 1u;
+                    const uint32_t s = col_of(j0, hit);
+                    if (hit && dead_in(s, gmin + word_at(j0))) kept &= ~(1u << j0);
+                }
+                nrec = (uint32_t)__popc(kept);
+            }
+        }
         // a list's task is pushed by the lane that owns the word: its first two lists out of the wave's reservation (le: the address's
         // word offset in `ext`, lc: the hash's chunk -- its lane's, number j0 >> 2 of the group), a third one by itself
         // (a gap mark among the lane's words takes one of the two turns without giving a task: a lane with two gaps before a list pushes
@@ -880,9 +965,16 @@ __device__ __forceinline__ void qs_body(const QSearchArgs& a, const GroupArgs& g
         auto next_list = [&](uint32_t& e, uint32_t& c) {                       // (the whole wave is here)
             const uint32_t j0 = cand != 0u ? (uint32_t)__builtin_ctz(cand) : 0u;
             c = (uint32_t)__shfl((int)chunk, (int)((lane & 56u) | (j0 >> 2)));
+            if constexpr (FILT) c |= col_of(j0, cand != 0u) << 8;               // ((FILT) the list's column rides above the chunk)
             e = cand != 0u ? word_at(j0) : 0xFFFFFFFFu;                        // (0xFFFFFFFF: a gap position, or nothing)
             cand &= cand - 1u;
         };
+        // (FILT) a list's task carries its column in bits 46..49 (the unfiltered form's pushes keep their own text, below: behind a
+        // lambda of both forms their instruction stream moved by two instructions)
+        auto list_task_filt = [&](uint32_t e, uint32_t c) -> unsigned long long {
+            return qs_task_list(s_ext[c & 63u] + (e & 0x7FFFFFFFu), c & 63u) | ((unsigned long long)(c >> 8) << 46);
+        };
+        (void)list_task_filt;
         if (__ballot((int)(cand != 0u)) != 0ull) {
             next_list(le[0], lc[0]);
             if (__ballot((int)(cand != 0u)) != 0ull) next_list(le[1], lc[1]);
@@ -896,11 +988,15 @@ __device__ __forceinline__ void qs_body(const QSearchArgs& a, const GroupArgs& g
             auto put_task = [&](unsigned long long e) { if (tat < TCAP) tasks[tat] = e; ++tat; };
 #pragma unroll
             for (uint32_t u = 0; u < 2u; ++u)
-                if (le[u] != 0xFFFFFFFFu) put_task(qs_task_list(s_ext[lc[u]] + (le[u] & 0x7FFFFFFFu), lc[u]));
+                if (le[u] != 0xFFFFFFFFu) {
+                    if constexpr (FILT) put_task(list_task_filt(le[u], lc[u]));
+                    else put_task(qs_task_list(s_ext[lc[u]] + (le[u] & 0x7FFFFFFFu), lc[u]));
+                }
             if (in_ext != 0u) {
                 const uint32_t* ob = s_ext[chunk] + ov;
                 for (uint32_t j = in_line; j < nwords;) {                      // (start + j >= inl here)
                     const uint32_t c = min(nwords - j, QS_TASK_WORDS);
+                    if constexpr (FILT) { if (tat < TCAP) tcols[tat] = qs_word_cols(pm, dm, j, c); }      // (the words' columns, as probe's put_words)
                     put_task(qs_task_words(ob + (start + j - inl), c, second >> j, chunk));
                     j += c;
                 }
@@ -909,7 +1005,8 @@ __device__ __forceinline__ void qs_body(const QSearchArgs& a, const GroupArgs& g
         while (__ballot((int)(cand != 0u)) != 0ull) {                            // (a lane with three lists among its words: hardly ever)
             uint32_t e, c;
             next_list(e, c);
-            if (e != 0xFFFFFFFFu) push_task(qs_task_list(s_ext[c] + (e & 0x7FFFFFFFu), c));
+            if constexpr (FILT) { if (e != 0xFFFFFFFFu) push_task(list_task_filt(e, c)); }
+            else if (e != 0xFFFFFFFFu) push_task(qs_task_list(s_ext[c] + (e & 0x7FFFFFFFu), c));
         }
     };
 
@@ -943,7 +1040,7 @@ __device__ __forceinline__ void qs_body(const QSearchArgs& a, const GroupArgs& g
     static_assert(QS_CH == 2, "the rounds run in pairs");
     if constexpr (MEM && PACK) mem_packed();
     for (uint32_t c = 0; c < pnchunks; ++c) {
-        if constexpr (!FILT) {
+        if constexpr (!FILT || COOP) {
             // a round after the other, each with its 64 lines per wave under way at once (the lane's registers hold one round's)
             QS_SUB0();
             QS_ARRIVED2(hq[0], hq[1]);
@@ -1097,6 +1194,7 @@ __device__ __forceinline__ void qs_body(const QSearchArgs& a, const GroupArgs& g
                         uint32_t doc = 0;
 #pragma unroll
                         for (uint32_t j = 0; j < QS_TASK_WORDS; ++j) doc = j == j0 ? d[j] : doc;
+                        if constexpr (COOP) { if (!union_hit(doc)) continue; }      // (the union bitmap first: a clear bit is live in every column)
                         if (dead_in(s, gmin + doc)) km &= ~(1u << j0);
                     }
                 }
@@ -1140,7 +1238,8 @@ __device__ __forceinline__ void qs_body(const QSearchArgs& a, const GroupArgs& g
                     for (uint32_t o2 = from; o2 < eff_s; o2 += 64u) {
                         bool kp = o2 + lane < eff_s;
                         const uint32_t dv = kp ? gload_u32(list + 1u + T_s + o2 + lane) : 0u;
-                        if constexpr (FILT) { if (kp) kp = !dead_in(col_s, gmin + dv); }
+                        if constexpr (FILT && COOP) { if (kp && union_hit(dv)) kp = !dead_in(col_s, gmin + dv); }
+                        else if constexpr (FILT) { if (kp) kp = !dead_in(col_s, gmin + dv); }
                         emit1(kp, dv);
                     }
                 }
@@ -1190,8 +1289,10 @@ __device__ __forceinline__ void qs_body(const QSearchArgs& a, const GroupArgs& g
     // ---- SearchResults.incr (src/common.zig:121-129), first the filter: every record into its doc's cell
     // (four records per lane and turn, read as one 16-byte piece: the loop is a chain of LDS latencies -- a record, then its cell)
     // (a lane's four are all records in every turn but the query's last: only that one tests record by record)
+    uint32_t tc4 = tid * 4u;                                 // ((COOP) likewise: the loop's first address is made here, not held from the kernel's start)
+    if constexpr (COOP) asm volatile("" : "+v"(tc4));
     if constexpr (!SHARE)
-    for (uint32_t i = tid * 4u; i < nrec; i += QS_WG * 4u) {
+    for (uint32_t i = tc4; i < nrec; i += QS_WG * 4u) {
         const uint4 r4 = *reinterpret_cast<const uint4*>(recs + i);             // (the array ends with four spare words)
         const uint32_t r[4] = {r4.x, r4.y, r4.z, r4.w};
         if (i + 3u < nrec) {
@@ -1656,6 +1757,22 @@ template <int NS, bool QS, bool MEM>
 __global__ __launch_bounds__(QS_WG) FPX_QS_OCC void k_search_low_filt(QSearchArgs a, GroupArgs ga)
 {
     qs_body<NS, QS, MEM, true, false, true>(a, ga);
+}
+
+// k_search_filt (option filt_coop = 1 under query_wg = 2): k_search_query's FILTERED job by the unfiltered form's rounds (qs_body: `COOP`) --
+// eight lanes to a line: one load instruction per line, the head's arithmetic and the per-hash statistics once, every inline word
+// classified where it landed.  What the per-lane walk needed every word's column for is done without: the hash's lane takes the words of
+// columns outside the snapshot out of the line's mask before it is broadcast; a kept doc is tested against the group's UNION dead-set
+// bitmap of the snapshot (bit doc - gmin, exactly what the word holds; QSearchArgs::redo), and only a doc whose bit is set -- a superseded
+// one, or its live rewrite in a newer column -- finds its column (pm | dm << 16 and start from the hash's lane) and runs the column's
+// exact test; a list's task carries its column the same way, `ext` words' tasks theirs from the hash's lane.  The tasks phase is the
+// filtered form's, with the union test in front of every exact one.  Tail, hand-back, queue of queries: k_search_query's.  No redo list.
+// Launched for ONE packed group whose snapshot holds the bitmap (or whose columns have no dead set); everything else that is filtered --
+// k_search_low_filt, k_search_next, k_search_window / k_search_packed -- keeps the per-lane walk.
+template <int NS, bool QS, bool MEM>
+__global__ __launch_bounds__(QS_WG) FPX_QS_OCC void k_search_filt(QSearchArgs a, GroupArgs ga)
+{
+    qs_body<NS, QS, MEM, true, false, false, false, false, false, true>(a, ga);
 }
 
 // k_search_next (option groups_wg = 1): k_search_query's body over a group that is not the first of its batch's (qs_body: `NEXT`) -- the

@@ -780,6 +780,16 @@ static void launch_search_query(bool ns8, bool qs, bool mem, bool filt, dim3 gri
 #undef FPX_LQ_MEM
 #undef FPX_LQ
 }
+// ... and k_search_filt's (the filtered form eight lanes to a line, behind the union dead-set bitmap: option filt_coop = 1 under query_wg = 2)
+static void launch_search_filt(bool ns8, bool qs, bool mem, dim3 grid, hipStream_t st, const QSearchArgs& qa, const GroupArgs& g)
+{
+#define FPX_LFC(NS, QSV, MEM) hipLaunchKernelGGL((k_search_filt<NS, QSV, MEM>), grid, dim3(QS_WG), QS_LDS_BYTES, st, qa, g)
+#define FPX_LFC_MEM(NS, QSV) do { if (mem) FPX_LFC(NS, QSV, true); else FPX_LFC(NS, QSV, false); } while (0)
+    if (ns8) { if (qs) FPX_LFC_MEM(8, true); else FPX_LFC_MEM(8, false); }
+    else { if (qs) FPX_LFC_MEM(16, true); else FPX_LFC_MEM(16, false); }
+#undef FPX_LFC_MEM
+#undef FPX_LFC
+}
 // ... and k_search_classes'
 static void launch_search_classes(bool ns8, bool mem, dim3 grid, hipStream_t st, const QSearchArgs& qa, const GroupArgs& g)
 {
@@ -964,6 +974,14 @@ static int run_query_wg(Batch& b, bool filt, bool low)
     qa.q_begin = 0u; qa.q_end = B;
     if (snap->n_mem != 0 && snap->mem_items != 0) { qa.mem_tab = snap->d_memtab; qa.mem_bucket = snap->d_membucket; qa.mem_bits = snap->d_membits; }
     if (hot_wg) { qa.redo = reinterpret_cast<unsigned long long*>(cs.extra); qa.redo_cap = B; }
+    // (option filt_coop = 1: ONE filtered packed group, no low floor in the batch, by k_search_filt -- where the snapshot holds the group's
+    // union dead-set bitmap (made under filt_coop = 1, the id range narrow enough) or no column has a dead set.  The bitmap travels in the
+    // redo list's members, which the filtered form never reads: fpx_qsearch.hpp, QSearchArgs)
+    const bool coop = filt && !low && ngroups == 1u && ctx_opt(snap->ctx, OPT_FILT_COOP) == 1 &&
+                      (snap->h_group[0].any_dead == 0u || (snap->dead_union && snap->dead_union->d_bits != nullptr));
+    if (coop && snap->h_group[0].any_dead != 0u) {
+        qa.redo = reinterpret_cast<unsigned long long*>(snap->dead_union->d_bits); qa.redo_cap = (uint32_t)(snap->dead_union->words - 1u);
+    }
     const GroupArgs gargs{snap->h_group[0], snap->d_direct};
     // as many workgroups as the chip holds at once (LDS: QS_WGS_PER_CU per CU); each takes every gridDim.x-th query
     const int cus = device_cus(snap->ctx);
@@ -998,6 +1016,7 @@ static int run_query_wg(Batch& b, bool filt, bool low)
         }
         else if (low && filt) launch_search_low_filt(ns8, b.want_q, qa.mem_tab != nullptr, grid, st, qa, gargs);
         else if (low) launch_search_low(ns8, b.want_q, qa.mem_tab != nullptr, grid, st, qa, gargs);
+        else if (coop) launch_search_filt(ns8, b.want_q, qa.mem_tab != nullptr, grid, st, qa, gargs);
         else launch_search_query(ns8, b.want_q, qa.mem_tab != nullptr, filt, grid, st, qa, gargs);
         if (up_chunks && c + 1u < up_chunks && (rc = upload_piece(b, c + 1u))) return rc;       // (the next piece crosses PCIe under this kernel)
     }
@@ -1022,7 +1041,7 @@ static int run_query_wg(Batch& b, bool filt, bool low)
         Cf = ws->h_counters[CTR_CANDS];
         if ((rc = finish_crowded(b, qa.sb, cs, to, Cf))) return rc;
     }
-    if ((rc = finish_wg_path(b, to, Cf, 4u | 64u | (filt ? 256u : 0u) | (R != 0 ? 1024u : 0u) | (low ? 4096u : 0u) | (ngroups > 1u ? 8192u : 0u)))) return rc;
+    if ((rc = finish_wg_path(b, to, Cf, 4u | 64u | (filt ? 256u : 0u) | (R != 0 ? 1024u : 0u) | (low ? 4096u : 0u) | (ngroups > 1u ? 8192u : 0u) | (coop ? 65536u : 0u)))) return rc;
     if (b.stats) b.stats->probe_launches += next_launches;
     return FPX_OK;
 }

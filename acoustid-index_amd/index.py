@@ -77,7 +77,10 @@ class Context:
         values above 2 are refused.  'shard_pack': 0 | 1 -- a step that 'shard_wg' lets walk its window gives a lane to every query hash
         of a round | packs the window's first occurrences before the rounds, a lane per probe, where the batch's longest query has at
         most 1024 hashes (Stats.path_flags bit 15, with bits 14, 6 and 4; the bins are the same, record for record); values above 1
-        are refused, and without 'shard_wg' it does nothing"""
+        are refused, and without 'shard_wg' it does nothing.  'filt_coop': 0 | 1 -- ONE packed group with superseded docs or masked
+        columns, under 'query_wg' 2, is walked a lane per hash with every word's column looked for | eight lanes to a line behind the
+        group's union dead-set bitmap, which a snapshot made under 1 holds (Segments.info()['dead_union_bytes']; Stats.path_flags bit
+        16, with bits 8 and 6; results and statistics are the same); values above 1 are refused"""
         check(lib().fpx_ctx_set_option(self.h, name.encode(), int(value)))
 
     def trim(self):
@@ -350,10 +353,10 @@ class Segments:
 
     def info(self):
         """fpx_snapshot_info as a dict"""
-        v = np.zeros(12, np.uint64)
-        check(lib().fpx_snapshot_info(self.h, _p(v), 12))
+        v = np.zeros(13, np.uint64)
+        check(lib().fpx_snapshot_info(self.h, _p(v), 13))
         keys = ("lean", "generic", "small", "direct_solo", "group_columns", "groups", "packed_groups", "memory", "settled_in_blocks", "bytes",
-                "one_launch_path", "block_form_files")
+                "one_launch_path", "block_form_files", "dead_union_bytes")
         return {k: int(x) for k, x in zip(keys, v)}
 
     def merge(self, sources, block_size=512):

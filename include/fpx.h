@@ -104,7 +104,10 @@ typedef struct {
                                    bit 14: a step of a sharded protocol walked its hash window a query per workgroup -- k_search_window:
                                    no keys, each query's records copied into its bin ("shard_wg" 1 | 2; bits 4 and 6 are set with it),
                                    bit 15: that walk was k_search_packed's -- the window's probes packed before the rounds ("shard_pack" 1
-                                   under "shard_wg"; bits 14, 6 and 4 are set with it).  fpx_sharded_search_batch: when every device's was */
+                                   under "shard_wg"; bits 14, 6 and 4 are set with it).  fpx_sharded_search_batch: when every device's was,
+                                   bit 16: the batch (or its part 0) ran k_search_filt -- the filtered form eight lanes to a line, behind
+                                   the group's union dead-set bitmap ("filt_coop" 1 under "query_wg" 2; bits 8 and 6 are set with it, and
+                                   bit 7 where it was part 0 of a snapshot in two parts) */
     uint64_t probe_kernel_fetched_bytes; /* block bytes the main probe kernel really fetched, in 128-byte lines: a probe
                                    whose hash the segment's presence bits know to be absent counts as a visited block (as in
                                    the reference) without the block being read, and a block that is read costs two lines up
@@ -214,6 +217,21 @@ int  fpx_ctx_device(const fpx_ctx *ctx);     /* the HIP ordinal the context live
  *                        k_search_window as under 0.  The bins, their counts and the statistics are the same, record for record; the
  *                        hand-back to the pipeline and its back-off are "shard_wg"'s.  Values above 1 are refused.  Without
  *                        "shard_wg" the option does nothing
+ *   "filt_coop"          0 | 1   ONE packed group with superseded docs and/or columns outside the snapshot, which "query_wg" 2 searches a
+ *                        query per workgroup, is walked by k_search_query's filtered form: a lane per hash, every word's column
+ *                        looked for (default 0) | by k_search_filt (csrc/fpx_qsearch.hpp; fpx_stats.path_flags bit 16, with bits 8
+ *                        and 6): the unfiltered form's rounds -- a line fetched once by eight lanes -- with every kept doc tested
+ *                        against the group's UNION dead-set bitmap of the snapshot (one bit per doc id of the group's range, set
+ *                        where any column's dead set holds the doc) and only a doc whose bit is set looking for its column and
+ *                        that column's own set.  Read TWICE: when a snapshot is made (fpx_snapshot_create builds the bitmap on the
+ *                        device -- for the snapshot's one packed group, or the group of its part 0 --, where the group has a dead
+ *                        set and its id range is at most 2^29 ids; fpx_snapshot_info slot 12 says how large it is) and per batch
+ *                        (the kernel: k_search_filt where the snapshot holds the bitmap or the group has no dead set).  A snapshot
+ *                        made under 0, or one whose id range was too wide, keeps the filtered k_search_query under 1.  Results and
+ *                        statistics are the same.  Values above 1 are refused.  The other filtered walks stay as they are under
+ *                        either value: k_search_low_filt ("low_wg" 2), k_search_next / k_search_low_next on filtered groups
+ *                        ("groups_wg"), k_search_window / k_search_packed ("shard_wg" 2), k_search_words ("words_wg" 2) and the
+ *                        pipeline's k_probe_pgroup.  Without "query_wg" 2 the option does nothing
  *   "fast"              1 | 0   the device-sized path (one host round trip per batch; default 1)
  *   "binned"             1 | 0   groups drop their records into bins of a few queries, scored a bin per workgroup (default 1)
  *   "rec32"              1 | 0   4-byte records in the bins where the doc ids leave room (default 1)
@@ -316,11 +334,12 @@ int fpx_segment_download(const fpx_segment *seg, uint8_t *blocks, size_t blocks_
  * then searched a query per workgroup while the option is 2. */
 int  fpx_snapshot_create(fpx_ctx *ctx, fpx_segment *const *segs, uint32_t num_segs, fpx_snapshot **out);
 /* acquireReader / IndexReader.deinit (src/Index.zig:430-434, :157-163) */
-/* What fpx_snapshot_create made of the segments on this context: info[0..11] = file segments searched in their blocks by the
+/* What fpx_snapshot_create made of the segments on this context: info[0..12] = file segments searched in their blocks by the
  * lean kernel, by the generic kernel, small ones searched in their decoded items, direct-addressed on their own, columns of
  * groups, groups, PACKED groups, memory segments, candidates that SETTLED in their blocks (no HBM for another form: see
  * fpx_segment_layout_reason), HBM bytes of the snapshot's segments, 1 = batches take the one-launch path (groups and nothing
- * else), block-form file segments in all. */
+ * else), block-form file segments in all, bytes of the union dead-set bitmap k_search_filt tests first (the snapshot's own or
+ * its part 0's; 0: none -- "filt_coop"). */
 int  fpx_snapshot_info(const fpx_snapshot *snap, uint64_t *info, uint32_t n);
 void fpx_snapshot_retain(fpx_snapshot *snap);
 void fpx_snapshot_release(fpx_snapshot *snap);
