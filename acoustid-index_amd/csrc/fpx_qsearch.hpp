@@ -32,25 +32,78 @@
 // Taken by run_batch for snapshots that are ONE packed group and nothing else (the resident index between merges), every column searched,
 // no superseded docs, queries of up to QS_MAX_HASHES hashes with a floor above 2; a query whose records outgrow the LDS array (hot
 // hashes: hundreds of docs per list) fails the batch over to the pipeline above (CTR_BINFAIL), which stays the path for everything else.
-// Option hot_wg = 1 (unfiltered only): such a query is named in the batch's redo list instead, with nothing counted for it, and
-// k_search_classes -- the same body, `CLS` -- walks it once per DOC CLASS, keeping one class of records each time: a doc's postings are
-// all in one class, so each pass counts exactly and the passes' candidates are disjoint.  The batch stays here and nothing backs off.
-// Option low_wg = 1 (unfiltered only): a batch with queries whose floor is 1 or 2 is taken too, by k_search_low -- the same body, `LOW`:
-// such a query's records are sorted in LDS and its scores read off the runs, only the top max_results leave.  A launch of k_search_low
-// carries no redo list: hot_wg is ignored for such a batch.  Option low_wg = 2: as 1, and under query_wg = 2 a FILTERED group too, by
-// k_search_low_filt -- the filtered walk below leaves live docs only in the record array, which is all the sorted tail asks for.
-// Option groups_wg = 1: a snapshot of several packed groups is walked group by group, k_search_next over the groups behind the first;
-// groups_wg = 2: as 1, and with low_wg a batch with floors of 1 or 2 too -- k_search_low (k_search_low_filt) over the first group,
-// k_search_low_next over the others.
-// Option shard_wg = 1 (fpx_shard_probe, a step of the sharded bin protocol): a rank's hash-window slice of a packed group is walked by
-// k_search_window -- the same body, `SHARE` --, the query's records copied into its bin instead of counted; 2: a filtered slice too.
-// Option shard_pack = 1 (under shard_wg): that walk by k_search_packed -- `SHARE` and `PACK` --, which tests the window first and packs
-// the window's first occurrences before the rounds: a lane per probe, not per query hash (queries of up to 1024 hashes).
-// FILT (option query_wg = 2): the same for a group with superseded docs and/or columns outside the snapshot (a live index between a
-// merge and its regroup) -- every word knows its column, as in k_probe_pgroup's per-column walk: a column outside `active` gives no
-// record and no statistic, a doc of a column with a dead set is dropped after it was counted (CTR_DOCS counts before supersession).
+//
+// THE FAMILY: nine kernels over one body, qs_body<V> -- V a qs_variant that NAMES what is on; what a form changes sits under
+// `if constexpr (<its flag>)`.  Every kernel takes the same two by-value parameters (QSearchArgs, GroupArgs): qs_cold_args()'s layout
+// holds for all of them.  NS: columns of a line (8 | 16); QS: per-query statistics; MEM: the memory segments' table (an instantiation of
+// its own: the look-up costs the usual one registers); FILT: a group with superseded docs and/or columns outside the snapshot.
+//
+//   kernel <parameters>                 | flags (qs_variant)  | context option = value            | launched by                             | lacks
+//   ------------------------------------+---------------------+-----------------------------------+-----------------------------------------+----------------------------------
+//   k_search_query    <NS,QS,MEM,FILT>  | --                  | query_wg = 1 (FILT: 2)            | run_query_wg, the first (only) group    | low floors
+//   k_search_classes  <NS,MEM>          | CLS  (QS on)        | hot_wg = 1                        | redo_hot_queries, the redo list's       | FILT, low floors, the queue of
+//                                       |                     |                                   | entries behind k_search_query           | queries, four workgroups per CU
+//   k_search_low      <NS,QS,MEM>       | LOW                 | low_wg = 1                        | run_query_wg, first group of a batch    | redo list (hot_wg ignored), FILT
+//                                       |                     |                                   | that HAS a floor of 1 or 2              |
+//   k_search_low_filt <NS,QS,MEM>       | LOW  (FILT on)      | low_wg = 2 under query_wg = 2     | the same, a filtered first group        | redo list
+//   k_search_filt     <NS,QS,MEM>       | COOP (FILT on)      | filt_coop = 1 under query_wg = 2  | run_query_wg, ONE filtered group whose  | redo list, low floors
+//                                       |                     |                                   | snapshot holds the union bitmap         |
+//   k_search_next     <NS,QS,FILT>      | NEXT                | groups_wg = 1                     | run_query_wg, groups 1 ..               | redo list, MEM, low floors
+//   k_search_low_next <NS,QS,FILT>      | LOW | NEXT          | groups_wg = 2 with low_wg         | run_query_wg, groups 1 .. of a batch    | redo list, MEM
+//                                       |                     |                                   | with a floor of 1 or 2                  |
+//   k_search_window   <NS,MEM,FILT>     | SHARE               | shard_wg = 1 (FILT: 2)            | shard_probe_impl (fpx_shard_probe)      | QS, redo list, low floors,
+//                                       |                     |                                   |                                         | filter, table, candidates
+//   k_search_packed   <NS,MEM,FILT>     | SHARE | PACK        | shard_pack = 1 under shard_wg     | shard_probe_impl, longest query of at   | the same
+//                                       |                     |                                   | most QS_PACK_MAX hashes                 |
+//
+// What the rows rest on:
+// CLS -- a query whose records outgrew the array is named in the batch's redo list, with nothing counted for it, and walked once per DOC
+//   CLASS, keeping one class of records each time: a doc's postings are all in one class, so each pass counts exactly and the passes'
+//   candidates are disjoint.  The batch stays here and nothing backs off.  The rare path: a query's walk C times over (its lines are in
+//   the L2 after the first).
+// LOW -- the legacy protocol's min_score 1, HTTP queries of 40 hashes or fewer.  For those the filter and the table are no use -- every
+//   doc counted is at or above the floor --: their tail SORTS the record array in place and reads the scores off the runs, only the top
+//   max_results leave; a query of the same batch with a floor above 2 takes the usual tail.  Launched for such a batch only.  With FILT
+//   (k_search_low_filt -- a name of its own: k_search_low keeps its three parameters) nothing more is needed: the filtered walk drops a
+//   superseded doc where it would be emitted, a column outside the snapshot gives no record, the memory segments' table holds live
+//   postings only -- when s_count is final the record array holds live docs only, which is all the sorted tail asks for.  Its scratch is
+//   the filter's area, which the task queue left before (tcols, behind the queue, was last read by the last task).  Blocks, docs, qstats
+//   and the histograms stay the filtered form's (counted before supersession).  No redo list under LOW: a query over QS_REC_CAP records
+//   (FILT: or over the filtered queue's QS_TASKS_FILT tasks) hands the batch to the pipeline, with the back-off.
+// FILT -- every word knows its column, as in k_probe_pgroup's per-column walk: a column outside `active` gives no record and no
+//   statistic, a doc of a column with a dead set is dropped after it was counted (CTR_DOCS counts before supersession).
+// COOP -- the filtered job by the unfiltered form's rounds, eight lanes to a line.  What the per-lane walk needed every word's column for
+//   is done without: the hash's lane takes the words of columns outside the snapshot out of the line's mask before it is broadcast; a
+//   kept doc is tested against the group's UNION dead-set bitmap of the snapshot (bit doc - gmin, exactly what the word holds), and only a
+//   doc whose bit is set -- a superseded one, or its live rewrite in a newer column -- finds its column (pm | dm << 16 and start from the
+//   hash's lane) and runs the column's exact test; a list's task carries its column the same way, `ext` words' tasks theirs from the
+//   hash's lane.  The tasks phase is the filtered form's, with the union test in front of every exact one.  Everything else that is
+//   filtered keeps the per-lane walk.
+// NEXT -- a snapshot of several packed groups is walked group by group, a launch each on the batch's stream.  A doc lives in one segment,
+//   hence in one group: every launch counts its docs whole and the launches' candidates are disjoint, so they only have to meet in the
+//   same slots and the same shared list -- the hand-over CHAINS behind what the launch before left in qcand_n[q], and qstats[q] is
+//   added to.  Everything else a launch reports is additive already (atomic adds and maxima into the batch's counters and sets).  The
+//   memory segments ride on the first group's launch.
+// LOW | NEXT -- the sorted tail's candidates -- each group's top max_results under its own raised floor, a superset of what k_finish
+//   keeps of the group -- go through the same buffer, flags and shared list into the chained hand-over.  What the composition rests on:
+//   the records become absolute ids with the gmin of THIS launch's group (the kernel's own GroupArgs); the sorted tail leaves its
+//   candidates where the usual one does -- cbuf, s_ccnt, s_cshared and the shared list --, its scratch is the filter's area, and it never
+//   touches s_claimed / s_full, which the chained hand-over takes behind the tail's last barrier; a query without a record here (or with
+//   fewer than its floor) skips both tails with s_ccnt = 0, and the hand-over then leaves the earlier launches' slots, count and mark as
+//   they are.  The floor a launch raises by its own group's best score is a lower bound of the one k_finish applies, and the union of
+//   every group's top max_results in (score descending, id ascending) order holds the snapshot's.
+// SHARE -- a rank's HASH-WINDOW slice of ONE group, for a step of the sharded bin protocol.  The dedup loop's window test leaves the other
+//   windows' hashes to their ranks; what a rank owes the protocol is the query's RECORDS, not its counts -- they go to the query's bin of
+//   2^QS_SHARE_BQ queries in the caller's send buffer, in bin_store's form (fpx_partition.hpp), one reservation per query.  MEM: the
+//   same table on every rank; only the window's hashes are looked up.  The record protocol keeps the low floors.
+// SHARE | PACK -- a rank of N sees 1 / N of a query's hashes: a hash outside the window never enters the set, the first occurrences
+//   inside it get dense places 0 .. m - 1 (a list in LDS, where the set was), every lane takes its hashes of the up to four rounds back
+//   from there, and the rounds are ceil(m / 256), not ceil(n / 256); a wave without a probe in a round skips its walk.  A lane to every
+//   PROBE, not to every hash of a round: one round at 4 and 8 ranks where k_search_window walks four, three waves in four idle in it at 8.
 #pragma once
 #include <hip/hip_runtime.h>
+
+#include <cstddef>
 
 #include "fpx_internal.h"
 
@@ -106,8 +159,14 @@ struct QSearchArgs {
     const uint32_t* hashes_base; const uint64_t* offsets;      // hashes_base[i]: the hash at ABSOLUTE position i of the batch; offsets[q] absolute
     const uint32_t* opts;                                      // [B][4]: max_results, floor, pct, raw length
     uint32_t q_begin, q_end, sb;                               // the launch's queries [q_begin, q_end) of the batch; sb: bits of the score field in a candidate key
-    uint64_t* cands; uint64_t cand_cap;                        // the shared candidate list (queries with more candidates than slots)
-    uint64_t* qcand; uint32_t* qcand_n;                        // the queries' own candidate slots
+    // Members in ONE LINE of a union share storage: a kernel that has no use for a member carries something of its own there under its
+    // own name, and the struct -- with it every other kernel's argument offsets, which qs_cold_args() reads by -- stays as it is.
+    //   SHARE (k_search_window, k_search_packed: no candidates, no slots, no redo list): bins, bin_cap, bin_fill, bin_rec32; qcand is null
+    //   COOP (k_search_filt: no redo list -- hot_wg is unfiltered-only): dead_union, dead_union_last
+    union { uint64_t* cands; uint64_t* bins; };                // the shared candidate list (queries with more candidates than slots) | the step's bins: [bin][bin_cap] records of 4 or 8 bytes
+    union { uint64_t cand_cap; uint64_t bin_cap; };            // its capacity | a bin's capacity in RECORDS
+    uint64_t* qcand;                                           // the queries' own candidate slots ...
+    union { uint32_t* qcand_n; uint32_t* bin_fill; };          // ... and their counts | the bins' fill counters (BIN_STRIDE words apart)
     unsigned long long* counters;
     unsigned long long* stat_sets;                             // [LEAN_STAT_SETS][8] statistics + [LEAN_STAT_SETS][HIST_SLOTS] histogram slots
     unsigned long long* qstats;                                // [B] blocks | docs << 32, or null
@@ -120,14 +179,10 @@ struct QSearchArgs {
     uint32_t stagger;                                          // delays of 3.4 us between the start of a CU's workgroups (0: none)
     // (option hot_wg = 1, unfiltered) the batch's redo list, or null: a query whose records outgrow the LDS array is named here --
     // q | its record total << 32, through CTR_REDO -- for k_search_classes instead of failing the batch (redo_cap: entries the list takes)
-    unsigned long long* redo; uint32_t redo_cap;
-    // k_search_window (SHARE) has no candidates, no slots and no redo list, and CARRIES THE STEP'S BINS IN THOSE MEMBERS -- the struct, and with
-    // it every other kernel's argument offsets, stays as it is: cands = the bins ([bin][cand_cap] records, 4 or 8 bytes each), cand_cap = a
-    // bin's capacity in RECORDS, qcand_n = the bins' fill counters (BIN_STRIDE words apart), redo_cap = 1: 4-byte records (bin_record32),
-    // 0: 8-byte ones; qcand and redo are null.
-    // k_search_filt (FILT and COOP) has no redo list either -- hot_wg is unfiltered-only -- and CARRIES THE GROUP'S UNION DEAD-SET BITMAP there, on
-    // the same terms: redo = the bitmap's words (32-bit, bit doc - gmin; Snapshot::dead_union) or null where no column has a dead set,
-    // redo_cap = the number of its LAST word (a word beyond it is not read).
+    // | the group's union dead-set bitmap of the snapshot (32-bit words, bit doc - gmin; Snapshot::dead_union), or null: no column has a dead set
+    union { unsigned long long* redo; const uint32_t* dead_union; };
+    // | 1: 4-byte records (bin_record32), 0: 8-byte ones | the number of the bitmap's LAST word (a word beyond it is not read)
+    union { uint32_t redo_cap; uint32_t bin_rec32; uint32_t dead_union_last; };
 };
 
 // The kernel's arguments as its two by-value parameters lay them out in the kernel-argument segment.  Most of them are needed once per
@@ -135,6 +190,8 @@ struct QSearchArgs {
 // of eight vector registers, which in turn spilled to scratch).  Those are read where they are used: qs_cold_args() is the segment's
 // address behind a barrier to hoisting, so that a load through it stays at its use and costs no register elsewhere.
 struct QSKernargs { QSearchArgs a; GroupArgs ga; };
+static_assert(sizeof(QSearchArgs) == 160 && offsetof(QSearchArgs, cands) == 40 && offsetof(QSearchArgs, qcand_n) == 64 && offsetof(QSearchArgs, next_q) == 128 &&
+              offsetof(QSearchArgs, redo) == 144 && offsetof(QSearchArgs, redo_cap) == 152, "QSearchArgs' layout is the kernels' argument segment: a member is renamed or shared, never moved");
 typedef const __attribute__((address_space(4))) QSKernargs* qs_kargs_t;
 __device__ __forceinline__ qs_kargs_t qs_cold_args()
 {
@@ -222,44 +279,27 @@ template <uint32_t K = 0, class F> __device__ __forceinline__ void qs_for8(F&& f
 #define QS_ARRIVED2(x, y) do { } while (0)
 #define QS_ARRIVED4(x) do { } while (0)
 #endif
-// (MEM: the snapshot has memory segments -- an instantiation of its own: their look-up costs the usual one registers.  FILT: the group has
-// superseded docs and/or columns outside the snapshot -- the supersession filter and the column masks, ga.segs' dead sets)
-// qs_body is both kernels: k_search_query (CLS false) and k_search_classes (CLS true, below) -- a redone query's walk is the same walk,
-// C times, keeping one class of docs each time; what differs sits under `if constexpr (CLS)`.
-constexpr uint32_t QS_MAX_CLASSES = 32;           // doc classes a redone query is searched in at most
+constexpr uint32_t QS_MAX_CLASSES = 32;           // (CLS) doc classes a redone query is searched in at most
 constexpr uint32_t QS_LIST_AHEAD = 8;             // (CLS) loads of 64 docs of a long list that a wave has under way at once
 // a record's doc class: bits of the doc's hash that neither the exact table's slot (h2 & TMASK) nor its pass selector ((h2 >> 16) % passes,
 // passes <= 64) looks at -- and qs_cell takes the doc's own bits, not its hash's --, so a class fills the filter and the table evenly
 __device__ __forceinline__ uint32_t qs_class(uint32_t rec) { return mix32(rec) >> 27; }
 static_assert(QS_MAX_CLASSES == 32u, "qs_class gives five bits");
-// ... and a third: k_search_low (LOW true, below; option low_wg = 1) -- the same walk for a batch that has queries with a floor of 1 or 2
-// -- and a fourth, the same with FILT: k_search_low_filt (option low_wg = 2) --
-// (the legacy protocol's min_score 1, HTTP queries of 40 hashes or fewer).  For those the filter and the table are no use -- every doc
-// counted is at or above the floor --: their tail SORTS the record array in place and reads the scores off the runs (under
-// `if constexpr (LOW)`, behind the statistics); a query of the same batch with a floor above 2 takes the tail below as it is.
 constexpr uint32_t QS_LOW_CHUNK = 8;              // (LOW) records a lane sorts in registers (two 16-byte pieces): the network's strides below it cost no barrier
-// ... and a fifth: k_search_next (NEXT true, below; option groups_wg = 1) -- the same walk over a group that is NOT THE FIRST of its
-// batch: a snapshot of several packed groups is walked group by group, a launch each on the batch's stream.  A doc lives in one segment,
-// hence in one group: every launch counts its docs whole and the launches' candidates are disjoint, so they only have to meet in the
-// same slots and the same shared list -- the hand-over CHAINS behind what the launch before left in qcand_n[q], and qstats[q] is
-// added to.  Everything else a launch reports is additive already (atomic adds and maxima into the batch's counters and sets).
-// ... and a sixth: k_search_low_next (LOW and NEXT true, below; option groups_wg = 2 with low_wg) -- a later group's walk for a batch
-// with floors of 1 or 2: the sorted tail's candidates -- each group's top max_results under its own raised floor, a superset of what
-// k_finish keeps of the group -- go through the same buffer, flags and shared list into the chained hand-over.
-// ... and a seventh: k_search_window (SHARE true, below; option shard_wg) -- the same walk over a rank's HASH-WINDOW slice of a group, for
-// a step of the sharded bin protocol (fpx_search.hip: shard_probe_impl).  The dedup loop's window test leaves the other windows' hashes to
-// their ranks; what a rank owes the protocol is the query's RECORDS, not its counts -- they go to the query's bin of 2^QS_SHARE_BQ queries
-// in the caller's send buffer, in bin_store's form (fpx_partition.hpp), one reservation per query.  No filter, no table, no candidates.
 constexpr uint32_t QS_SHARE_BQ = 3;               // (SHARE) queries per bin: fpx_search.hip's SHARD_BQ
 constexpr uint32_t QS_SHARE_STRIDE = 32;          // (SHARE) 32-bit words between the bins' fill counters: fpx_partition.hpp's BIN_STRIDE
-// ... and an eighth: k_search_packed (SHARE and PACK true, below; option shard_pack) -- the window's walk with the window's PROBES packed
-// before the rounds.  A rank of N sees 1 / N of a query's hashes: under `PACK` a hash outside the window never enters the set, the first
-// occurrences inside it get dense places 0 .. m - 1 (a list in LDS, where the set was), every lane takes its hashes of the up to four
-// rounds back from there, and the rounds are ceil(m / 256), not ceil(n / 256); a wave without a probe in a round skips its walk.
 constexpr uint32_t QS_PACK_MAX = 4u * QS_WG;      // (PACK) longest query taken: what hq[] holds.  A longer one hands the step back (CTR_BINFAIL 1)
-template <int NS, bool QS, bool MEM, bool FILT, bool CLS, bool LOW = false, bool NEXT = false, bool SHARE = false, bool PACK = false, bool COOP = false>
-__device__ __forceinline__ void qs_body(const QSearchArgs& a, const GroupArgs& ga)
-{
+
+// A kernel of the family, NAMED: what every one has a value for (NS, QS, MEM, FILT), and the forms that are on (the head comment's table).
+// Which forms go together is this type's business: an illegal combination fails where it is written.
+enum : uint32_t { QS_F_CLS = 1u, QS_F_LOW = 2u, QS_F_NEXT = 4u, QS_F_SHARE = 8u, QS_F_PACK = 16u, QS_F_COOP = 32u };
+template <int NS_, bool QS_, bool MEM_, bool FILT_, uint32_t FORM = 0u>
+struct qs_variant {
+    static constexpr int NS = NS_;
+    static constexpr bool QS = QS_, MEM = MEM_, FILT = FILT_;
+    static constexpr bool CLS = (FORM & QS_F_CLS) != 0u, LOW = (FORM & QS_F_LOW) != 0u, NEXT = (FORM & QS_F_NEXT) != 0u;
+    static constexpr bool SHARE = (FORM & QS_F_SHARE) != 0u, PACK = (FORM & QS_F_PACK) != 0u, COOP = (FORM & QS_F_COOP) != 0u;
+    static_assert(NS == 8 || NS == 16, "columns of a line");
     static_assert(!COOP || (FILT && !CLS && !LOW && !NEXT && !SHARE), "the filtered walk eight lanes to a line: k_search_filt only");
     static_assert(!SHARE || (!QS && !CLS && !LOW && !NEXT), "a window's walk for the bin protocol: no per-query statistics, no doc classes, no sorted tail, one group");
     static_assert(!PACK || SHARE, "packed probes: a window's walk only (without a window nearly every hash is a probe)");
@@ -268,6 +308,13 @@ __device__ __forceinline__ void qs_body(const QSearchArgs& a, const GroupArgs& g
     static_assert(!(CLS && FILT), "doc classes: the unfiltered walk only");
     static_assert(!LOW || (!CLS && QS_WG == 256u && QS_REC_CAP >= 512u && (QS_REC_CAP & (QS_REC_CAP - 1u)) == 0u),
                   "low floors: no doc classes; the sorted tail's scans are written for 256 lanes and a power-of-two array");
+};
+
+template <class V>
+__device__ __forceinline__ void qs_body(const QSearchArgs& a, const GroupArgs& ga)
+{
+    constexpr int NS = V::NS;
+    constexpr bool QS = V::QS, MEM = V::MEM, FILT = V::FILT, CLS = V::CLS, LOW = V::LOW, NEXT = V::NEXT, SHARE = V::SHARE, PACK = V::PACK, COOP = V::COOP;
 #ifdef FPX_QS_PROF
     unsigned long long t_prev = clock64(), t_sub = 0;
 #endif
@@ -542,11 +589,11 @@ __device__ __forceinline__ void qs_body(const QSearchArgs& a, const GroupArgs& g
         return di != 0xFFFFFFFFu && is_dead_seg(ga.segs[di], doc);
     };
     // (COOP) the group's UNION dead-set bitmap of this snapshot -- bit doc - gmin: some column's dead set holds the doc --, words 0 .. ub_last,
-    // or null: no column has a dead set.  In QSearchArgs::redo / redo_cap, which the filtered form has no other use for.  A doc whose bit is
+    // or null: no column has a dead set (QSearchArgs::dead_union / dead_union_last).  A doc whose bit is
     // clear is live whatever its column; one whose bit is set asks its own column's set (dead_in)
     const uint32_t* ub = nullptr;
     uint32_t ub_last = 0u;
-    if constexpr (COOP) { ub = reinterpret_cast<const uint32_t*>(a.redo); ub_last = a.redo_cap; }
+    if constexpr (COOP) { ub = a.dead_union; ub_last = a.dead_union_last; }
     auto union_hit = [&](uint32_t rel) -> bool {            // (rel: doc - gmin, what a word holds)
         const uint32_t i = rel >> 5;
         return ub != nullptr && i <= ub_last && ((gload_u32(ub + i) >> (rel & 31u)) & 1u) != 0u;
@@ -1507,9 +1554,8 @@ __device__ __forceinline__ void qs_body(const QSearchArgs& a, const GroupArgs& g
       }
     }
     if constexpr (SHARE) {
-        // ---- (SHARE) the query's records of this window leave for its bin, bin q >> QS_SHARE_BQ of the step's send buffer -- the members
-        //      this kernel has no other use for carry it (QSearchArgs): cands the bins, cand_cap a bin's capacity in records, qcand_n the
-        //      bins' fill counters, redo_cap the record width.  ONE reservation per query -- nrec is final: the barrier above --, the base
+        // ---- (SHARE) the query's records of this window leave for its bin, bin q >> QS_SHARE_BQ of the step's send buffer (QSearchArgs:
+        //      bins, bin_cap, bin_fill, bin_rec32).  ONE reservation per query -- nrec is final: the barrier above --, the base
         //      to the workgroup through LDS; every lane copies.  A place at or beyond the capacity is not stored, the fill counter runs
         //      past it: k_cell_counts and the host learn the need from it.  The record is bin_store's (fpx_partition.hpp): narrow,
         //      doc << 3 | q & 7 -- a doc that leaves no room, or would read as "no record", raises CTR_BINFAIL to 3 and the host redoes
@@ -1518,12 +1564,12 @@ __device__ __forceinline__ void qs_body(const QSearchArgs& a, const GroupArgs& g
         (void)floor_q; (void)smax; (void)low_q; (void)filter; (void)table; (void)cbuf; (void)TMASK;
         if (s_over_recs == 0u && s_count <= QS_REC_CAP && nrec != 0u) {      // (uniform: LDS words behind a barrier)
             const uint32_t bn = q >> QS_SHARE_BQ;
-            if (tid == 0) s_cbase_lo = atomicAdd(&kt->a.qcand_n[(size_t)bn * QS_SHARE_STRIDE], nrec);
+            if (tid == 0) s_cbase_lo = atomicAdd(&kt->a.bin_fill[(size_t)bn * QS_SHARE_STRIDE], nrec);
             __syncthreads();
-            const uint64_t base = s_cbase_lo, cap = kt->a.cand_cap;
+            const uint64_t base = s_cbase_lo, cap = kt->a.bin_cap;
             const uint32_t gmin_c = kt->ga.g.gmin;
-            if (kt->a.redo_cap != 0u) {                                        // (uniform)
-                uint32_t* const dst = reinterpret_cast<uint32_t*>(kt->a.cands) + (size_t)bn * cap;
+            if (kt->a.bin_rec32 != 0u) {                                       // (uniform)
+                uint32_t* const dst = reinterpret_cast<uint32_t*>(kt->a.bins) + (size_t)bn * cap;
                 bool wide = false;
                 for (uint32_t i = tid; i < nrec; i += QS_WG) {
                     const uint32_t doc = recs[i] + gmin_c;
@@ -1534,7 +1580,7 @@ __device__ __forceinline__ void qs_body(const QSearchArgs& a, const GroupArgs& g
                 }
                 if (wide) atomicMax(&kt->a.counters[CTR_BINFAIL], 3ull);
             } else {
-                uint64_t* const dst = kt->a.cands + (size_t)bn * cap;
+                uint64_t* const dst = kt->a.bins + (size_t)bn * cap;
                 for (uint32_t i = tid; i < nrec; i += QS_WG)
                     if (base + i < cap) dst[base + i] = ((uint64_t)q << 32) | (uint32_t)(recs[i] + gmin_c);
             }
@@ -1720,106 +1766,51 @@ __device__ __forceinline__ void qs_body(const QSearchArgs& a, const GroupArgs& g
   }
 }
 
+// The nine kernels (the head comment's table): a wrapper names what is on.
 template <int NS, bool QS, bool MEM, bool FILT>
 __global__ __launch_bounds__(QS_WG) FPX_QS_OCC void k_search_query(QSearchArgs a, GroupArgs ga)
 {
-    qs_body<NS, QS, MEM, FILT, false>(a, ga);
+    qs_body<qs_variant<NS, QS, MEM, FILT>>(a, ga);
 }
-
-// k_search_classes: the queries that k_search_query named in the batch's redo list (option hot_wg = 1; a.q_begin .. a.q_end are entries of
-// that list), each searched once per doc class.  The same two by-value parameters: qs_cold_args()'s layout holds for both kernels.
-// The rare path: a query's walk C times over (its lines are in the L2 after the first), four workgroups per CU not asked for.
 template <int NS, bool MEM>
 __global__ __launch_bounds__(QS_WG) FPX_QS_OCC void k_search_classes(QSearchArgs a, GroupArgs ga)
 {
-    qs_body<NS, true, MEM, false, true>(a, ga);
+    qs_body<qs_variant<NS, true, MEM, false, QS_F_CLS>>(a, ga);
 }
-
-// k_search_low (option low_wg = 1): k_search_query's unfiltered body for a batch that HAS queries with a floor of 1 or 2 -- those take the
-// sorted tail (qs_body: `LOW`), the batch's other queries the usual one.  Launched for such a batch only: every other batch is
-// k_search_query's, whatever the option says.  No redo list (a.redo is null: option hot_wg is ignored for such a batch -- a query whose
-// records outgrow the array hands the batch to the pipeline, with the back-off) and no doc classes.  The same two by-value parameters.
 template <int NS, bool QS, bool MEM>
 __global__ __launch_bounds__(QS_WG) FPX_QS_OCC void k_search_low(QSearchArgs a, GroupArgs ga)
 {
-    qs_body<NS, QS, MEM, false, false, true>(a, ga);
+    qs_body<qs_variant<NS, QS, MEM, false, QS_F_LOW>>(a, ga);
 }
-
-// k_search_low_filt (option low_wg = 2 under query_wg = 2): the same for a group with superseded docs and/or columns outside the snapshot
-// -- k_search_query's FILTERED body with the sorted tail.  The filtered walk drops a superseded doc where it would be emitted (the lane's
-// own words, the tasks' words and list heads, the wave-walked lists), a column outside the snapshot gives no record, the memory segments'
-// table holds live postings only: when s_count is final the record array holds live docs only, as doc - gmin -- what the tail takes as it
-// is.  Its scratch is the filter's area, which the task queue left before (tcols, behind the queue, was last read by the last task).
-// Blocks, docs, qstats and the histograms are the filtered form's (counted before supersession); no redo list; a query over QS_REC_CAP
-// records or over the filtered queue's QS_TASKS_FILT tasks hands the batch to the pipeline.  A kernel of its own name: k_search_low keeps
-// its three parameters.
 template <int NS, bool QS, bool MEM>
 __global__ __launch_bounds__(QS_WG) FPX_QS_OCC void k_search_low_filt(QSearchArgs a, GroupArgs ga)
 {
-    qs_body<NS, QS, MEM, true, false, true>(a, ga);
+    qs_body<qs_variant<NS, QS, MEM, true, QS_F_LOW>>(a, ga);
 }
-
-// k_search_filt (option filt_coop = 1 under query_wg = 2): k_search_query's FILTERED job by the unfiltered form's rounds (qs_body: `COOP`) --
-// eight lanes to a line: one load instruction per line, the head's arithmetic and the per-hash statistics once, every inline word
-// classified where it landed.  What the per-lane walk needed every word's column for is done without: the hash's lane takes the words of
-// columns outside the snapshot out of the line's mask before it is broadcast; a kept doc is tested against the group's UNION dead-set
-// bitmap of the snapshot (bit doc - gmin, exactly what the word holds; QSearchArgs::redo), and only a doc whose bit is set -- a superseded
-// one, or its live rewrite in a newer column -- finds its column (pm | dm << 16 and start from the hash's lane) and runs the column's
-// exact test; a list's task carries its column the same way, `ext` words' tasks theirs from the hash's lane.  The tasks phase is the
-// filtered form's, with the union test in front of every exact one.  Tail, hand-back, queue of queries: k_search_query's.  No redo list.
-// Launched for ONE packed group whose snapshot holds the bitmap (or whose columns have no dead set); everything else that is filtered --
-// k_search_low_filt, k_search_next, k_search_window / k_search_packed -- keeps the per-lane walk.
 template <int NS, bool QS, bool MEM>
 __global__ __launch_bounds__(QS_WG) FPX_QS_OCC void k_search_filt(QSearchArgs a, GroupArgs ga)
 {
-    qs_body<NS, QS, MEM, true, false, false, false, false, false, true>(a, ga);
+    qs_body<qs_variant<NS, QS, MEM, true, QS_F_COOP>>(a, ga);
 }
-
-// k_search_next (option groups_wg = 1): k_search_query's body over a group that is not the first of its batch's (qs_body: `NEXT`) -- the
-// chained hand-over, qstats added to.  No redo list (a.redo is null), no low floors, no memory table: the memory segments ride on the
-// first group's launch, an ordinary k_search_query.  The same two by-value parameters.
 template <int NS, bool QS, bool FILT>
 __global__ __launch_bounds__(QS_WG) FPX_QS_OCC void k_search_next(QSearchArgs a, GroupArgs ga)
 {
-    qs_body<NS, QS, false, FILT, false, false, true>(a, ga);
+    qs_body<qs_variant<NS, QS, false, FILT, QS_F_NEXT>>(a, ga);
 }
-
-// k_search_low_next (option groups_wg = 2 with low_wg): the same over a later group for a batch that HAS queries with a floor of 1 or 2
-// (qs_body: `LOW` and `NEXT`) -- those take the sorted tail, the batch's other queries the usual one, and both end in the chained
-// hand-over.  The first group's launch is k_search_low or k_search_low_filt.  What the composition rests on: the records become absolute
-// ids with the gmin of THIS launch's group (the kernel's own GroupArgs); the sorted tail leaves its candidates where the usual one does
-// -- cbuf, s_ccnt, s_cshared and the shared list --, its scratch is the filter's area, and it never touches s_claimed / s_full, which
-// the chained hand-over takes behind the tail's last barrier; a query without a record here (or with fewer than its floor) skips both
-// tails with s_ccnt = 0, and the hand-over then leaves the earlier launches' slots, count and mark as they are; qstats[q] is added to.
-// The floor a launch raises by its own group's best score is a lower bound of the one k_finish applies, and the union of every group's
-// top max_results in (score descending, id ascending) order holds the snapshot's.  FILT as in k_search_low_filt; no memory table.
 template <int NS, bool QS, bool FILT>
 __global__ __launch_bounds__(QS_WG) FPX_QS_OCC void k_search_low_next(QSearchArgs a, GroupArgs ga)
 {
-    qs_body<NS, QS, false, FILT, false, true, true>(a, ga);
+    qs_body<qs_variant<NS, QS, false, FILT, QS_F_LOW | QS_F_NEXT>>(a, ga);
 }
-
-// k_search_window (option shard_wg): k_search_query's body over a rank's hash-window slice of ONE packed group, for a step of the sharded
-// bin protocol (qs_body: `SHARE`) -- the walk as it stands, the window test in its dedup loop, and in place of the counting tail the
-// query's records copied into its bin of the caller's send buffer.  MEM: the memory segments' table (the same on every rank; only the
-// window's hashes are looked up).  FILT (option shard_wg = 2): a slice with superseded docs or columns outside the snapshot -- live docs
-// only reach the record array.  No per-query statistics (fpx_shard_probe has none), no redo list, no low floors (the record protocol
-// keeps them).  The same two by-value parameters: qs_cold_args()'s layout holds.
 template <int NS, bool MEM, bool FILT>
 __global__ __launch_bounds__(QS_WG) FPX_QS_OCC void k_search_window(QSearchArgs a, GroupArgs ga)
 {
-    qs_body<NS, false, MEM, FILT, false, false, false, true>(a, ga);
+    qs_body<qs_variant<NS, false, MEM, FILT, QS_F_SHARE>>(a, ga);
 }
-
-// k_search_packed (option shard_pack, under shard_wg): k_search_window's walk with the window's probes PACKED before the rounds (qs_body:
-// `PACK`) -- for batches whose longest query has at most QS_PACK_MAX hashes.  At N ranks a query's 1000 hashes leave 1000 / N probes:
-// k_search_window gives a lane to every HASH of a round, this one to every PROBE -- one round at 4 and 8 ranks where that one walks four,
-// three waves in four idle in it at 8.  Records, statistics, the cancel point, the queue of queries and the tail are k_search_window's.
-// The same two by-value parameters: qs_cold_args()'s layout holds.
 template <int NS, bool MEM, bool FILT>
 __global__ __launch_bounds__(QS_WG) FPX_QS_OCC void k_search_packed(QSearchArgs a, GroupArgs ga)
 {
-    qs_body<NS, false, MEM, FILT, false, false, false, true, true>(a, ga);
+    qs_body<qs_variant<NS, false, MEM, FILT, QS_F_SHARE | QS_F_PACK>>(a, ga);
 }
 
 // zeroes what a batch of k_search_query adds to: the batch's counters and the statistics sets (one launch instead of two memsets)

@@ -169,21 +169,34 @@ static int sort_keys(Workspace* ws, uint64_t* pair[2], uint64_t n, unsigned lo, 
     return FPX_OK;
 }
 
-// k_probe_group's instantiations: columns of a directory line (8 | 16), records binned in the flush, per-query scan statistics
+// ---- the one launcher of kernel templates K<NS, flags...>: run-time flags become compile-time constants, IN ORDER, and that instantiation
+// is launched.  The flags at a call site stand in the kernel's OWN template-parameter order, behind ns8 (NS: 8 | 16 columns of a directory
+// line).  A flag is a `bool` and nothing else: a pointer or a count in a flag's place does not compile.
+template <class F> static void with_flags(F&& f) { f(); }
+template <class F, class B, class... Bs> static void with_flags(F&& f, B flag, Bs... rest)
+{
+    static_assert(std::is_same<B, bool>::value, "a kernel's flag is a bool");
+    if (flag) with_flags([&](auto... cs) { f(std::true_type{}, cs...); }, rest...);
+    else with_flags([&](auto... cs) { f(std::false_type{}, cs...); }, rest...);
+}
+template <class F, class... Bs> static void with_ns(bool ns8, F&& f, Bs... flags)
+{
+    if (ns8) with_flags([&](auto... cs) { f(std::integral_constant<int, 8>{}, cs...); }, flags...);
+    else with_flags([&](auto... cs) { f(std::integral_constant<int, 16>{}, cs...); }, flags...);
+}
+// (a macro: a function template's name cannot be passed as an argument.  a0, a1: the kernel's two by-value parameters)
+#define FPX_LAUNCH(K, grid, wg, lds, st, a0, a1, ns8, ...) \
+    with_ns(ns8, [&](auto ns, auto... cs) { hipLaunchKernelGGL((K<decltype(ns)::value, decltype(cs)::value...>), grid, dim3(wg), lds, st, a0, a1); }, __VA_ARGS__)
+// (the query-per-workgroup family of fpx_qsearch.hpp: one workgroup size, one LDS size)
+#define FPX_LAUNCH_QS(K, grid, st, qa, g, ns8, ...) FPX_LAUNCH(K, grid, QS_WG, QS_LDS_BYTES, st, qa, g, ns8, __VA_ARGS__)
+
+// k_probe_group<NS, BINNED, QS> -- records binned in the flush, per-query scan statistics --, or k_probe_pgroup for a dense group: its words
+// live in its lines (fpx_pgroup.hpp)
 static void launch_probe_group(bool packed, bool ns8, bool binned, bool qs, dim3 grid, hipStream_t st, const ProbeArgs& a, const GroupArgs& g)
 {
-    const size_t dyn = (size_t)FSTAGE_CAP * sizeof(uint64_t) + (binned ? (size_t)FSTAGE_CAP * sizeof(uint16_t) : 0u);       // stage (+ ranks)
-    const size_t dyn_packed = (size_t)FSTAGE_CAP * sizeof(uint64_t) + PK_HEAD_LDS;      // (+ the prefetched line heads)
-#define FPX_LP(K, LDS, NS, BN, QSV) hipLaunchKernelGGL((K<NS, BN, QSV>), grid, dim3(FK_WG), LDS, st, a, g)
-#define FPX_LP_QS(K, LDS, NS, BN) do { if (qs) FPX_LP(K, LDS, NS, BN, true); else FPX_LP(K, LDS, NS, BN, false); } while (0)
-#define FPX_LP_BN(K, LDS, NS) do { if (binned) FPX_LP_QS(K, LDS, NS, true); else FPX_LP_QS(K, LDS, NS, false); } while (0)
-#define FPX_LP_NS(K, LDS) do { if (ns8) FPX_LP_BN(K, LDS, 8); else FPX_LP_BN(K, LDS, 16); } while (0)
-    if (packed) FPX_LP_NS(k_probe_pgroup, dyn_packed);      // a dense group: its words live in its lines (fpx_pgroup.hpp)
-    else FPX_LP_NS(k_probe_group, dyn);
-#undef FPX_LP_NS
-#undef FPX_LP_BN
-#undef FPX_LP_QS
-#undef FPX_LP
+    const size_t stage = (size_t)FSTAGE_CAP * sizeof(uint64_t);
+    if (packed) FPX_LAUNCH(k_probe_pgroup, grid, FK_WG, stage + PK_HEAD_LDS, st, a, g, ns8, binned, qs);      // (+ the prefetched line heads)
+    else FPX_LAUNCH(k_probe_group, grid, FK_WG, stage + (binned ? (size_t)FSTAGE_CAP * sizeof(uint16_t) : 0u), st, a, g, ns8, binned, qs);      // (+ ranks)
 }
 
 constexpr int FPX_SPLIT = 1;   // internal: candidate key does not fit 64 bits, split the batch
@@ -767,97 +780,6 @@ static bool takes_words_wg(const Snapshot* snap, const uint64_t* offsets, const 
 }
 
 // ---- A. a query per workgroup --------------------------------------------------------------------------------------------------------
-// k_search_query's instantiations: columns of a directory line (8 | 16), per-query scan statistics, the memory segments' table, filtered
-static void launch_search_query(bool ns8, bool qs, bool mem, bool filt, dim3 grid, hipStream_t st, const QSearchArgs& qa, const GroupArgs& g)
-{
-#define FPX_LQ(NS, QSV, MEM, FILT) hipLaunchKernelGGL((k_search_query<NS, QSV, MEM, FILT>), grid, dim3(QS_WG), QS_LDS_BYTES, st, qa, g)
-#define FPX_LQ_MEM(NS, QSV, FILT) do { if (mem) FPX_LQ(NS, QSV, true, FILT); else FPX_LQ(NS, QSV, false, FILT); } while (0)
-#define FPX_LQ_QS(NS, FILT) do { if (qs) FPX_LQ_MEM(NS, true, FILT); else FPX_LQ_MEM(NS, false, FILT); } while (0)
-#define FPX_LQ_NS(FILT) do { if (ns8) FPX_LQ_QS(8, FILT); else FPX_LQ_QS(16, FILT); } while (0)
-    if (filt) FPX_LQ_NS(true); else FPX_LQ_NS(false);
-#undef FPX_LQ_NS
-#undef FPX_LQ_QS
-#undef FPX_LQ_MEM
-#undef FPX_LQ
-}
-// ... and k_search_filt's (the filtered form eight lanes to a line, behind the union dead-set bitmap: option filt_coop = 1 under query_wg = 2)
-static void launch_search_filt(bool ns8, bool qs, bool mem, dim3 grid, hipStream_t st, const QSearchArgs& qa, const GroupArgs& g)
-{
-#define FPX_LFC(NS, QSV, MEM) hipLaunchKernelGGL((k_search_filt<NS, QSV, MEM>), grid, dim3(QS_WG), QS_LDS_BYTES, st, qa, g)
-#define FPX_LFC_MEM(NS, QSV) do { if (mem) FPX_LFC(NS, QSV, true); else FPX_LFC(NS, QSV, false); } while (0)
-    if (ns8) { if (qs) FPX_LFC_MEM(8, true); else FPX_LFC_MEM(8, false); }
-    else { if (qs) FPX_LFC_MEM(16, true); else FPX_LFC_MEM(16, false); }
-#undef FPX_LFC_MEM
-#undef FPX_LFC
-}
-// ... and k_search_classes'
-static void launch_search_classes(bool ns8, bool mem, dim3 grid, hipStream_t st, const QSearchArgs& qa, const GroupArgs& g)
-{
-#define FPX_LC(NS, MEM) hipLaunchKernelGGL((k_search_classes<NS, MEM>), grid, dim3(QS_WG), QS_LDS_BYTES, st, qa, g)
-    if (ns8) { if (mem) FPX_LC(8, true); else FPX_LC(8, false); }
-    else { if (mem) FPX_LC(16, true); else FPX_LC(16, false); }
-#undef FPX_LC
-}
-// ... and k_search_low's (a batch with queries whose floor is 1 or 2, option low_wg; unfiltered)
-static void launch_search_low(bool ns8, bool qs, bool mem, dim3 grid, hipStream_t st, const QSearchArgs& qa, const GroupArgs& g)
-{
-#define FPX_LL(NS, QSV, MEM) hipLaunchKernelGGL((k_search_low<NS, QSV, MEM>), grid, dim3(QS_WG), QS_LDS_BYTES, st, qa, g)
-#define FPX_LL_MEM(NS, QSV) do { if (mem) FPX_LL(NS, QSV, true); else FPX_LL(NS, QSV, false); } while (0)
-    if (ns8) { if (qs) FPX_LL_MEM(8, true); else FPX_LL_MEM(8, false); }
-    else { if (qs) FPX_LL_MEM(16, true); else FPX_LL_MEM(16, false); }
-#undef FPX_LL_MEM
-#undef FPX_LL
-}
-// ... and k_search_low_filt's (the same on a filtered group: option low_wg = 2 under query_wg = 2)
-static void launch_search_low_filt(bool ns8, bool qs, bool mem, dim3 grid, hipStream_t st, const QSearchArgs& qa, const GroupArgs& g)
-{
-#define FPX_LF(NS, QSV, MEM) hipLaunchKernelGGL((k_search_low_filt<NS, QSV, MEM>), grid, dim3(QS_WG), QS_LDS_BYTES, st, qa, g)
-#define FPX_LF_MEM(NS, QSV) do { if (mem) FPX_LF(NS, QSV, true); else FPX_LF(NS, QSV, false); } while (0)
-    if (ns8) { if (qs) FPX_LF_MEM(8, true); else FPX_LF_MEM(8, false); }
-    else { if (qs) FPX_LF_MEM(16, true); else FPX_LF_MEM(16, false); }
-#undef FPX_LF_MEM
-#undef FPX_LF
-}
-// ... and k_search_next's (a group that is not the first of its batch's: option groups_wg = 1)
-static void launch_search_next(bool ns8, bool qs, bool filt, dim3 grid, hipStream_t st, const QSearchArgs& qa, const GroupArgs& g)
-{
-#define FPX_LN(NS, QSV, FILT) hipLaunchKernelGGL((k_search_next<NS, QSV, FILT>), grid, dim3(QS_WG), QS_LDS_BYTES, st, qa, g)
-#define FPX_LN_FILT(NS, QSV) do { if (filt) FPX_LN(NS, QSV, true); else FPX_LN(NS, QSV, false); } while (0)
-    if (ns8) { if (qs) FPX_LN_FILT(8, true); else FPX_LN_FILT(8, false); }
-    else { if (qs) FPX_LN_FILT(16, true); else FPX_LN_FILT(16, false); }
-#undef FPX_LN_FILT
-#undef FPX_LN
-}
-// ... and k_search_low_next's (the same for a batch with queries whose floor is 1 or 2: option groups_wg = 2 with low_wg)
-static void launch_search_low_next(bool ns8, bool qs, bool filt, dim3 grid, hipStream_t st, const QSearchArgs& qa, const GroupArgs& g)
-{
-#define FPX_LLN(NS, QSV, FILT) hipLaunchKernelGGL((k_search_low_next<NS, QSV, FILT>), grid, dim3(QS_WG), QS_LDS_BYTES, st, qa, g)
-#define FPX_LLN_FILT(NS, QSV) do { if (filt) FPX_LLN(NS, QSV, true); else FPX_LLN(NS, QSV, false); } while (0)
-    if (ns8) { if (qs) FPX_LLN_FILT(8, true); else FPX_LLN_FILT(8, false); }
-    else { if (qs) FPX_LLN_FILT(16, true); else FPX_LLN_FILT(16, false); }
-#undef FPX_LLN_FILT
-#undef FPX_LLN
-}
-// ... and k_search_window's (a rank's hash-window slice, a step of the sharded bin protocol: option shard_wg)
-static void launch_search_window(bool ns8, bool mem, bool filt, dim3 grid, hipStream_t st, const QSearchArgs& qa, const GroupArgs& g)
-{
-#define FPX_LW(NS, MEM, FILT) hipLaunchKernelGGL((k_search_window<NS, MEM, FILT>), grid, dim3(QS_WG), QS_LDS_BYTES, st, qa, g)
-#define FPX_LW_FILT(NS, MEM) do { if (filt) FPX_LW(NS, MEM, true); else FPX_LW(NS, MEM, false); } while (0)
-    if (ns8) { if (mem) FPX_LW_FILT(8, true); else FPX_LW_FILT(8, false); }
-    else { if (mem) FPX_LW_FILT(16, true); else FPX_LW_FILT(16, false); }
-#undef FPX_LW_FILT
-#undef FPX_LW
-}
-// ... and k_search_packed's (the same slice with the window's probes packed before the rounds: option shard_pack under shard_wg)
-static void launch_search_packed(bool ns8, bool mem, bool filt, dim3 grid, hipStream_t st, const QSearchArgs& qa, const GroupArgs& g)
-{
-#define FPX_LP(NS, MEM, FILT) hipLaunchKernelGGL((k_search_packed<NS, MEM, FILT>), grid, dim3(QS_WG), QS_LDS_BYTES, st, qa, g)
-#define FPX_LP_FILT(NS, MEM) do { if (filt) FPX_LP(NS, MEM, true); else FPX_LP(NS, MEM, false); } while (0)
-    if (ns8) { if (mem) FPX_LP_FILT(8, true); else FPX_LP_FILT(8, false); }
-    else { if (mem) FPX_LP_FILT(16, true); else FPX_LP_FILT(16, false); }
-#undef FPX_LP_FILT
-#undef FPX_LP
-}
 // a query-per-workgroup path opens: the queries' candidate slots (`extra_words` of the caller's behind them), the counters and statistics
 // sets zeroed, the probe's first event -- and the arguments every such kernel takes, from the batch (Args: QFrameArgs | QSearchArgs,
 // by their same-named members; which queries a launch takes is the caller's to say)
@@ -925,7 +847,7 @@ static int redo_hot_queries(Batch& b, QSearchArgs qa, const GroupArgs& gargs, bo
     }
     int rc;
     qa.q_begin = 0u; qa.q_end = (uint32_t)R; qa.next_q = nullptr; qa.stagger = 0u;      // (entries of the list; all pieces of a chunked upload have arrived)
-    launch_search_classes(ns8, qa.mem_tab != nullptr, dim3(std::min<uint32_t>((uint32_t)R, (uint32_t)cus * QS_WGS_PER_CU)), b.st, qa, gargs);
+    FPX_LAUNCH_QS(k_search_classes, dim3(std::min<uint32_t>((uint32_t)R, (uint32_t)cus * QS_WGS_PER_CU)), b.st, qa, gargs, ns8, qa.mem_tab != nullptr);
     if ((rc = publish(b, true))) return rc;
     FPX_HIP(hipEventRecord(b.ws->ev_end, b.st));
     FPX_SYNC_BATCH(b);
@@ -975,14 +897,15 @@ static int run_query_wg(Batch& b, bool filt, bool low)
     if (snap->n_mem != 0 && snap->mem_items != 0) { qa.mem_tab = snap->d_memtab; qa.mem_bucket = snap->d_membucket; qa.mem_bits = snap->d_membits; }
     if (hot_wg) { qa.redo = reinterpret_cast<unsigned long long*>(cs.extra); qa.redo_cap = B; }
     // (option filt_coop = 1: ONE filtered packed group, no low floor in the batch, by k_search_filt -- where the snapshot holds the group's
-    // union dead-set bitmap (made under filt_coop = 1, the id range narrow enough) or no column has a dead set.  The bitmap travels in the
-    // redo list's members, which the filtered form never reads: fpx_qsearch.hpp, QSearchArgs)
+    // union dead-set bitmap (made under filt_coop = 1, the id range narrow enough) or no column has a dead set.  The bitmap shares the
+    // redo list's storage, which the filtered form never reads: fpx_qsearch.hpp, QSearchArgs)
     const bool coop = filt && !low && ngroups == 1u && ctx_opt(snap->ctx, OPT_FILT_COOP) == 1 &&
                       (snap->h_group[0].any_dead == 0u || (snap->dead_union && snap->dead_union->d_bits != nullptr));
     if (coop && snap->h_group[0].any_dead != 0u) {
-        qa.redo = reinterpret_cast<unsigned long long*>(snap->dead_union->d_bits); qa.redo_cap = (uint32_t)(snap->dead_union->words - 1u);
+        qa.dead_union = snap->dead_union->d_bits; qa.dead_union_last = (uint32_t)(snap->dead_union->words - 1u);
     }
     const GroupArgs gargs{snap->h_group[0], snap->d_direct};
+    const bool filt0 = group_filtered(snap->h_group[0]), mem = qa.mem_tab != nullptr;
     // as many workgroups as the chip holds at once (LDS: QS_WGS_PER_CU per CU); each takes every gridDim.x-th query
     const int cus = device_cus(snap->ctx);
     const uint32_t up_chunks = b.up_chunks;
@@ -996,28 +919,25 @@ static int run_query_wg(Batch& b, bool filt, bool low)
         qa.stagger = alone ? QS_STAGGER : 0u;
         if (up_chunks) FPX_HIP(hipStreamWaitEvent(st, ws->ev_chunk[c], 0));           // (the piece's hashes have arrived; the next piece is on its way)
         const dim3 grid(std::min<uint32_t>(qa.q_end - qa.q_begin, (uint32_t)cus * QS_WGS_PER_CU));
+        // (the piece's queries over group 0 -- filtered or not as that group is: with one group, takes_query_wg's `filt` --, with the memory table)
+        if (low && filt0) FPX_LAUNCH_QS(k_search_low_filt, grid, st, qa, gargs, ns8, b.want_q, mem);
+        else if (low) FPX_LAUNCH_QS(k_search_low, grid, st, qa, gargs, ns8, b.want_q, mem);
+        else if (coop) FPX_LAUNCH_QS(k_search_filt, grid, st, qa, gargs, ns8, b.want_q, mem);
+        else FPX_LAUNCH_QS(k_search_query, grid, st, qa, gargs, ns8, b.want_q, mem, filt0);
         if (ngroups > 1u) {
-            // (the piece's queries over group 0, then over every other group: a launch's queue of queries is a word of its own.
+            // (... then over every other group: a launch's queue of queries is a word of its own.
             // low -- option groups_wg = 2 --: the kernels with the sorted tail, each launch filtered or not as its own group is)
-            const bool filt0 = group_filtered(snap->h_group[0]);
-            if (low && filt0) launch_search_low_filt(ns8, b.want_q, qa.mem_tab != nullptr, grid, st, qa, gargs);
-            else if (low) launch_search_low(ns8, b.want_q, qa.mem_tab != nullptr, grid, st, qa, gargs);
-            else launch_search_query(ns8, b.want_q, qa.mem_tab != nullptr, filt0, grid, st, qa, gargs);
             QSearchArgs qn = qa;
             qn.mem_tab = nullptr; qn.mem_bucket = nullptr; qn.mem_bits = nullptr;
             for (uint32_t gi = 1; gi < ngroups; ++gi) {
                 qn.next_q = qa.next_q ? ws->d_def_count + (size_t)gi * Workspace::UP_CHUNKS + c : nullptr;
                 const bool ns8_g = snap->groups[gi]->ns == 8u, filt_g = group_filtered(snap->h_group[gi]);
                 const GroupArgs gargs_g{snap->h_group[gi], snap->d_direct};
-                if (low) launch_search_low_next(ns8_g, b.want_q, filt_g, grid, st, qn, gargs_g);
-                else launch_search_next(ns8_g, b.want_q, filt_g, grid, st, qn, gargs_g);
+                if (low) FPX_LAUNCH_QS(k_search_low_next, grid, st, qn, gargs_g, ns8_g, b.want_q, filt_g);
+                else FPX_LAUNCH_QS(k_search_next, grid, st, qn, gargs_g, ns8_g, b.want_q, filt_g);
                 ++next_launches;
             }
         }
-        else if (low && filt) launch_search_low_filt(ns8, b.want_q, qa.mem_tab != nullptr, grid, st, qa, gargs);
-        else if (low) launch_search_low(ns8, b.want_q, qa.mem_tab != nullptr, grid, st, qa, gargs);
-        else if (coop) launch_search_filt(ns8, b.want_q, qa.mem_tab != nullptr, grid, st, qa, gargs);
-        else launch_search_query(ns8, b.want_q, qa.mem_tab != nullptr, filt, grid, st, qa, gargs);
         if (up_chunks && c + 1u < up_chunks && (rc = upload_piece(b, c + 1u))) return rc;       // (the next piece crosses PCIe under this kernel)
     }
     // (the batch's counters and statistics sets go to the host's mapped copies here, after the first pass, and again after a redo)
@@ -1065,17 +985,6 @@ static int run_side_wg(Batch& b)
     return finish_wg_path(b, to, Cf, 512u);
 }
 
-// k_search_words' instantiations: columns of a directory line (8 | 16), the memory segments' table, filtered
-static void launch_search_words(bool ns8, bool mem, bool filt, dim3 grid, hipStream_t st, const WordsArgs& wa, const GroupArgs& g)
-{
-#define FPX_LW(NS, MEM, FILT) hipLaunchKernelGGL((k_search_words<NS, MEM, FILT>), grid, dim3(QF_WG), QF_LDS_BYTES, st, wa, g)
-#define FPX_LW_MEM(NS, FILT) do { if (mem) FPX_LW(NS, true, FILT); else FPX_LW(NS, false, FILT); } while (0)
-#define FPX_LW_NS(FILT) do { if (ns8) FPX_LW_MEM(8, FILT); else FPX_LW_MEM(16, FILT); } while (0)
-    if (filt) FPX_LW_NS(true); else FPX_LW_NS(false);
-#undef FPX_LW_NS
-#undef FPX_LW_MEM
-#undef FPX_LW
-}
 // ... and a group in directory + words form, by k_search_words (the memory segments behind their table with it)
 static int run_words_wg(Batch& b, bool filt)
 {
@@ -1088,7 +997,8 @@ static int run_words_wg(Batch& b, bool filt)
     const GroupArgs gargs{snap->h_group[0], snap->d_direct};
     // as many workgroups as the chip holds at once (LDS: QF_WGS_PER_CU per CU); each takes every gridDim.x-th query
     const int cus = device_cus(snap->ctx);
-    launch_search_words(snap->groups[0]->ns == 8u, wa.mem_tab != nullptr, filt, dim3(std::min<uint32_t>(B, (uint32_t)cus * QF_WGS_PER_CU)), b.st, wa, gargs);
+    FPX_LAUNCH(k_search_words, dim3(std::min<uint32_t>(B, (uint32_t)cus * QF_WGS_PER_CU)), QF_WG, QF_LDS_BYTES, b.st, wa, gargs,
+               snap->groups[0]->ns == 8u, wa.mem_tab != nullptr, filt);
     ResultsTo to;
     if ((rc = close_wg_pass(b, wa.f.sb, cs, &to))) return rc;           // (handed back: the pipeline)
     const uint64_t Cf = b.ws->h_counters[CTR_CANDS];
@@ -2360,15 +2270,16 @@ int shard_probe_impl(Snapshot* snap, const QueryBatch* qb, uint32_t world, uint3
                 qa.hashes_base = qb->d_hashes; qa.offsets = qb->d_offsets; qa.opts = qb->d_opts; qa.q_begin = 0u; qa.q_end = B; qa.sb = 32u - qbits;
                 qa.counters = ws->d_counters; qa.stat_sets = reinterpret_cast<unsigned long long*>(d_stats32); qa.qstats = nullptr; qa.cancel = cancel;
                 if (snap->n_mem != 0 && snap->mem_items != 0) { qa.mem_tab = snap->d_memtab; qa.mem_bucket = snap->d_membucket; qa.mem_bits = snap->d_membits; }
-                // (the bins ride in the members k_search_window has no other use for: QSearchArgs)
-                qa.cands = d_send; qa.cand_cap = rec_cap; qa.qcand = nullptr; qa.qcand_n = ws->d_cells; qa.redo = nullptr; qa.redo_cap = rec32;
+                // (the step's bins: no candidates, no slots, no redo list -- QSearchArgs)
+                qa.bins = d_send; qa.bin_cap = rec_cap; qa.bin_fill = ws->d_cells; qa.bin_rec32 = rec32;
                 // (the launch's queue of queries: a word behind the overflow flag, zeroed with the cells)
                 qa.next_q = FPX_QS_DYN ? d_overflow + 4 : nullptr; qa.stagger = 0u;
                 const GroupArgs gargs{snap->h_group[0], snap->d_direct};
                 const dim3 grid(std::min<uint32_t>(B, (uint32_t)device_cus(snap->ctx) * QS_WGS_PER_CU));
                 FPX_HIP(hipEventRecord(ws->ev_probe0, st));
-                if (pack) launch_search_packed(snap->groups[0]->ns == 8u, qa.mem_tab != nullptr, group_filtered(snap->h_group[0]), grid, st, qa, gargs);
-                else launch_search_window(snap->groups[0]->ns == 8u, qa.mem_tab != nullptr, group_filtered(snap->h_group[0]), grid, st, qa, gargs);
+                const bool ns8 = snap->groups[0]->ns == 8u, mem = qa.mem_tab != nullptr, filt = group_filtered(snap->h_group[0]);
+                if (pack) FPX_LAUNCH_QS(k_search_packed, grid, st, qa, gargs, ns8, mem, filt);
+                else FPX_LAUNCH_QS(k_search_window, grid, st, qa, gargs, ns8, mem, filt);
                 FPX_HIP(hipEventRecord(ws->ev_probe1, st));
                 hipLaunchKernelGGL(k_cell_counts, dim3((ncells + 255) / 256), dim3(256), 0, st, (const unsigned int*)ws->d_cells, ncells, d_send_counts, ws->d_counters,
                                    rec32 << 31);

@@ -1,5 +1,5 @@
-"""The reader of the kernel-resources tests (test_kernel_resources.py and its siblings for k_search_classes, k_search_low,
-k_search_low_filt, k_search_side and k_search_words): what the compiler made of every kernel in the built gfx950 code objects, read the
+"""The reader of the kernel-resources tests (test_qs_kernel_resources.py: the nine kernels over qs_body, a table, and four older files of one kernel each; test_side_kernel_resources.py
+and test_words_kernel_resources.py: k_search_side and k_search_words): what the compiler made of every kernel in the built gfx950 code objects, read the
 way tools/kernel_resources.py reads them (llvm-readelf --notes on the code objects bundled in libfpx.so, or in build/fpx_search.o).
 A helper module like fpx_testlib.py: no test, no fixture."""
 import functools

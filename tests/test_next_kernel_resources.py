@@ -1,6 +1,6 @@
 """What the compiler made of k_search_next (csrc/fpx_qsearch.hpp, option groups_wg = 1: k_search_query's walk over a group that is not the
 first of its batch's, the hand-over chained behind the launch before), read from the built code object the way
-tests/test_low_filt_kernel_resources.py reads k_search_low_filt's: its eight instantiations (8 / 16 columns x QS x FILT; never MEM)
+tests/test_qs_kernel_resources.py reads the other kernels of the family: its eight instantiations (8 / 16 columns x QS x FILT; never MEM)
 exist and no other; none is above 128 vector registers or 106 scalar ones; the static LDS is 784 bytes at most unfiltered and 848
 filtered -- with the dynamic 39 KB four workgroups share a CU --; and none has more scratch than k_search_query<NS, QS, false, FILT> in the
 same code object.  No GPU needed."""

@@ -1,4 +1,4 @@
-"""What the compiler made of k_search_side (csrc/fpx_qside.hpp), read from the built code object the way tests/test_kernel_resources.py
+"""What the compiler made of k_search_side (csrc/fpx_qside.hpp), read from the built code object the way tests/test_qs_kernel_resources.py
 reads k_search_query's: the kernel exists, has no scratch segment and spills no vector register, and its registers and static LDS leave
 room for four workgroups on a CU next to the 39 KB of dynamic LDS it is launched with -- no GPU needed."""
 import re

@@ -1,4 +1,4 @@
-"""What the compiler made of k_search_words (csrc/fpx_qwords.hpp), read from the built code object the way tests/test_kernel_resources.py
+"""What the compiler made of k_search_words (csrc/fpx_qwords.hpp), read from the built code object the way tests/test_qs_kernel_resources.py
 reads k_search_query's: its eight instantiations (8 / 16 columns x MEM x FILT) exist, none is above 128 vector registers (four workgroups
 per CU next to 39 KB of dynamic LDS each), the unfiltered ones have no scratch segment and spill no vector register, and the static LDS
 leaves room for four workgroups in a CU's 160 KB -- no GPU needed."""
