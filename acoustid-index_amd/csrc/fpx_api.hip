@@ -424,7 +424,7 @@ static const OptInfo OPT_TABLE[OPT_COUNT] = {
     /* OPT_SIDE_WG */            {"side_wg", "FPX_SIDE_WG", 0, 0, false},                        // 0 | 1: the file segments next to the group (small decoded, direct-addressed alone) by the pipeline | a query per workgroup (fpx_qside.hpp)
     /* OPT_HOT_WG */             {"hot_wg", "FPX_HOT_WG", 0, 0, false},                          // 0 | 1: a query whose records outgrow k_search_query's LDS array hands the batch to the pipeline | is redone in doc classes by k_search_classes (fpx_qsearch.hpp; unfiltered only)
     /* OPT_WORDS_WG */           {"words_wg", "FPX_WORDS_WG", 0, 0, false},                      // 0 | 1 | 2: a snapshot that is ONE group in directory + words form by the pipeline | a query per workgroup (fpx_qwords.hpp) | as 1, a group with superseded docs or masked columns too
-    /* OPT_LOW_WG */             {"low_wg", "FPX_LOW_WG", 0, 0, false},                          // 0 | 1 | 2: a batch with queries whose floor is 1 or 2 (the legacy protocol, short fingerprints) goes to the pipeline | stays with k_search_query's path, by k_search_low (fpx_qsearch.hpp; one packed, unfiltered group) | as 1, a group with superseded docs or masked columns too (k_search_low_filt; such a group is on that path under query_wg 2 only)
+    /* OPT_LOW_WG */             {"low_wg", "FPX_LOW_WG", 0, 0, false},                          // 0 | 1 | 2 | 3: a batch with queries whose floor is 1 or 2 (the legacy protocol, short fingerprints) goes to the pipeline | stays with k_search_query's path, by k_search_low (fpx_qsearch.hpp; one packed, unfiltered group) | as 1, a group with superseded docs or masked columns too (k_search_low_filt; such a group is on that path under query_wg 2 only) | as 2, and ONE filtered group that filt_coop = 1 would give to k_search_filt -- the snapshot holds the union bitmap, or no column has a dead set -- by k_search_low_coop: eight lanes to a line and the sorted tail; everything else as under 2
     /* OPT_GROUPS_WG */          {"groups_wg", "FPX_GROUPS_WG", 0, 0, false},                    // 0 | 1 | 2: a snapshot of SEVERAL packed groups keeps the largest for k_search_query and sends the others through the pipeline | walks up to QS_MAX_GROUPS of them one after the other a query per workgroup (k_search_next, fpx_qsearch.hpp; read per batch, and when a snapshot's two parts are made) | as 1, a batch with queries whose floor is 1 or 2 too where low_wg allows it (1: no group filtered, 2: any; k_search_low / k_search_low_filt over the first group, k_search_low_next over the others)
     /* OPT_SHARD_WG */           {"shard_wg", "FPX_SHARD_WG", 0, 0, false},                      // 0 | 1 | 2: a step of the sharded bin protocol (fpx_shard_probe) on a rank whose snapshot is ONE packed group with its hash window (+ memory segments behind their table) makes and orders the window's keys and probes them (the pipeline) | walks the window a query per workgroup and copies each query's records into its bin (k_search_window, fpx_qsearch.hpp; unfiltered) | as 1, a group with superseded docs or masked columns too
     /* OPT_SHARD_PACK */         {"shard_pack", "FPX_SHARD_PACK", 0, 0, false},                  // 0 | 1: a step that shard_wg lets walk its window does so by k_search_window, a lane per query HASH and round | by k_search_packed, which packs the window's first occurrences before the rounds -- a lane per PROBE -- where the batch's longest query has at most 1024 hashes (fpx_qsearch.hpp; a longer one keeps the batch on k_search_window).  Nothing without shard_wg

@@ -27,13 +27,14 @@
 // words are the hash's, which of them second words of doubles; and, before the loads, the line's number in the group --, and every lane
 // classifies its own four words of each line where they landed: every inline word is walked, only lists and words in `ext` are tasks.
 // The filtered form keeps the per-lane walk (a word's column is bookkeeping of its own) -- but for k_search_filt (`COOP`, option
-// filt_coop = 1): the same rounds for a filtered group, a word's column looked for only where the group's union dead-set bitmap says so.
+// filt_coop = 1) and k_search_low_coop (`LOW | COOP`, with option low_wg = 3): the same rounds for a filtered group, a word's column
+// looked for only where the group's union dead-set bitmap says so.
 //
 // Taken by run_batch for snapshots that are ONE packed group and nothing else (the resident index between merges), every column searched,
 // no superseded docs, queries of up to QS_MAX_HASHES hashes with a floor above 2; a query whose records outgrow the LDS array (hot
 // hashes: hundreds of docs per list) fails the batch over to the pipeline above (CTR_BINFAIL), which stays the path for everything else.
 //
-// THE FAMILY: nine kernels over one body, qs_body<V> -- V a qs_variant that NAMES what is on; what a form changes sits under
+// THE FAMILY: ten kernels over one body, qs_body<V> -- V a qs_variant that NAMES what is on; what a form changes sits under
 // `if constexpr (<its flag>)`.  Every kernel takes the same two by-value parameters (QSearchArgs, GroupArgs): qs_cold_args()'s layout
 // holds for all of them.  NS: columns of a line (8 | 16); QS: per-query statistics; MEM: the memory segments' table (an instantiation of
 // its own: the look-up costs the usual one registers); FILT: a group with superseded docs and/or columns outside the snapshot.
@@ -48,6 +49,8 @@
 //   k_search_low_filt <NS,QS,MEM>       | LOW  (FILT on)      | low_wg = 2 under query_wg = 2     | the same, a filtered first group        | redo list
 //   k_search_filt     <NS,QS,MEM>       | COOP (FILT on)      | filt_coop = 1 under query_wg = 2  | run_query_wg, ONE filtered group whose  | redo list, low floors
 //                                       |                     |                                   | snapshot holds the union bitmap         |
+//   k_search_low_coop <NS,QS,MEM>       | LOW | COOP (FILT on)| low_wg = 3 with filt_coop = 1     | the same, a batch that HAS a floor of   | redo list
+//                                       |                     | under query_wg = 2                | 1 or 2                                  |
 //   k_search_next     <NS,QS,FILT>      | NEXT                | groups_wg = 1                     | run_query_wg, groups 1 ..               | redo list, MEM, low floors
 //   k_search_low_next <NS,QS,FILT>      | LOW | NEXT          | groups_wg = 2 with low_wg         | run_query_wg, groups 1 .. of a batch    | redo list, MEM
 //                                       |                     |                                   | with a floor of 1 or 2                  |
@@ -79,6 +82,14 @@
 //   hash's lane) and runs the column's exact test; a list's task carries its column the same way, `ext` words' tasks theirs from the
 //   hash's lane.  The tasks phase is the filtered form's, with the union test in front of every exact one.  Everything else that is
 //   filtered keeps the per-lane walk.
+// LOW | COOP -- the two compose without new machinery: LOW changes only the query's tail, COOP only the rounds and the tasks' tests, and
+//   COOP leaves live docs only in the record array as the per-lane filtered walk does -- a kept word whose union bit is clear is live in
+//   every column, one whose bit is set ran its column's exact test before it was emitted --, which is all the sorted tail asks for.
+//   Nothing of the rounds or the tasks is live in the filter's area or the queue when the tail takes them as scratch: the tasks loop ends
+//   behind a barrier with every task and its tcols word read, the filter's atomics behind the tail's first.  A query of the same launch
+//   with a floor above 2 takes the usual tail.  Registers: what the tail makes of the lane's number is taken afresh there (lt, llane), as
+//   load_pair's `t` and the filter loop's `tc4` are, and the relative floor is worked out in 32 bits -- held from the kernel's start
+//   across the rounds they were 20 bytes of scratch at 16 columns.  The union bitmap rides where the redo list would: LOW has none.
 // NEXT -- a snapshot of several packed groups is walked group by group, a launch each on the batch's stream.  A doc lives in one segment,
 //   hence in one group: every launch counts its docs whole and the launches' candidates are disjoint, so they only have to meet in the
 //   same slots and the same shared list -- the hand-over CHAINS behind what the launch before left in qcand_n[q], and qstats[q] is
@@ -162,7 +173,7 @@ struct QSearchArgs {
     // Members in ONE LINE of a union share storage: a kernel that has no use for a member carries something of its own there under its
     // own name, and the struct -- with it every other kernel's argument offsets, which qs_cold_args() reads by -- stays as it is.
     //   SHARE (k_search_window, k_search_packed: no candidates, no slots, no redo list): bins, bin_cap, bin_fill, bin_rec32; qcand is null
-    //   COOP (k_search_filt: no redo list -- hot_wg is unfiltered-only): dead_union, dead_union_last
+    //   COOP (k_search_filt, k_search_low_coop: no redo list -- hot_wg is unfiltered-only, and LOW has none): dead_union, dead_union_last
     union { uint64_t* cands; uint64_t* bins; };                // the shared candidate list (queries with more candidates than slots) | the step's bins: [bin][bin_cap] records of 4 or 8 bytes
     union { uint64_t cand_cap; uint64_t bin_cap; };            // its capacity | a bin's capacity in RECORDS
     uint64_t* qcand;                                           // the queries' own candidate slots ...
@@ -300,7 +311,7 @@ struct qs_variant {
     static constexpr bool CLS = (FORM & QS_F_CLS) != 0u, LOW = (FORM & QS_F_LOW) != 0u, NEXT = (FORM & QS_F_NEXT) != 0u;
     static constexpr bool SHARE = (FORM & QS_F_SHARE) != 0u, PACK = (FORM & QS_F_PACK) != 0u, COOP = (FORM & QS_F_COOP) != 0u;
     static_assert(NS == 8 || NS == 16, "columns of a line");
-    static_assert(!COOP || (FILT && !CLS && !LOW && !NEXT && !SHARE), "the filtered walk eight lanes to a line: k_search_filt only");
+    static_assert(!COOP || (FILT && !CLS && !NEXT && !SHARE), "the filtered walk eight lanes to a line: k_search_filt, and with the sorted tail k_search_low_coop");
     static_assert(!SHARE || (!QS && !CLS && !LOW && !NEXT), "a window's walk for the bin protocol: no per-query statistics, no doc classes, no sorted tail, one group");
     static_assert(!PACK || SHARE, "packed probes: a window's walk only (without a window nearly every hash is a probe)");
     static_assert(!PACK || 2u * QS_PACK_MAX <= QS_REC_CAP, "the packed list and its memory-table bits live at the record array's bottom");
@@ -1407,6 +1418,15 @@ __device__ __forceinline__ void qs_body(const QSearchArgs& a, const GroupArgs& g
       //      k_finish gets a superset of what it keeps, in the usual keys.  The filter's area is scratch: a histogram of min(score, 255),
       //      the waves' totals, M, T and the quota.
       if (low_q && s_over_recs == 0u && !q_redo && nrec != 0u && nrec >= floor_q && kt->a.opts[(size_t)q * 4u] != 0u) {
+        // ((COOP) the lane's number is taken afresh for the tail, as load_pair's `t` and the filter's `tc4` are: what the tail makes of it --
+        // lsc's slot of the lane's wave, the slot lane 255 writes T to, half a dozen comparisons -- does not change from query to query,
+        // was made at the kernel's start and held across the rounds: in k_search_low_coop<16, ..> that was 20 bytes of scratch.  Every
+        // other kernel's lt and llane ARE its tid and lane)
+        uint32_t lt_own = tid;
+        if constexpr (COOP) asm volatile("" : "+v"(lt_own));
+        const uint32_t llane_own = lt_own & 63u;
+        const uint32_t& lt = COOP ? lt_own : tid;
+        const uint32_t& llane = COOP ? llane_own : lane;
         const uint32_t kmax = kt->a.opts[(size_t)q * 4u], pct = kt->a.opts[(size_t)q * 4u + 2u];
         const uint32_t gmin_c = kt->ga.g.gmin;
         uint32_t* const lhist = filter;                      // [256]: docs by min(score, 255)
@@ -1414,9 +1434,9 @@ __device__ __forceinline__ void qs_body(const QSearchArgs& a, const GroupArgs& g
         uint32_t P = 512u;
         while (P < nrec) P <<= 1;                            // (<= QS_REC_CAP)
         __syncthreads();                                     // (the filter's atomics and everybody's reads of the records are done)
-        for (uint32_t i = tid; i < P; i += QS_WG) recs[i] = i < nrec ? recs[i] + gmin_c : 0xFFFFFFFFu;
-        lhist[tid] = 0u;
-        if (tid < 8u) lsc[tid] = 0u;
+        for (uint32_t i = lt; i < P; i += QS_WG) recs[i] = i < nrec ? recs[i] + gmin_c : 0xFFFFFFFFu;
+        lhist[lt] = 0u;
+        if (lt < 8u) lsc[lt] = 0u;
         __syncthreads();
         // (2) the network.  A lane keeps QS_LOW_CHUNK consecutive places in registers for the strides below that -- no barrier between
         // them --; the strides from QS_LOW_CHUNK up are four compare-exchanges per lane and turn on 16-byte pieces, a barrier each
@@ -1425,7 +1445,7 @@ __device__ __forceinline__ void qs_body(const QSearchArgs& a, const GroupArgs& g
             x = up ? lo : hi; y = up ? hi : lo;
         };
         auto chunk_sort = [&](uint32_t k) {                  // k == 0: the merge steps 2, 4 and 8 whole; else step k's strides 4, 2, 1
-            for (uint32_t c = tid; c < P / QS_LOW_CHUNK; c += QS_WG) {
+            for (uint32_t c = lt; c < P / QS_LOW_CHUNK; c += QS_WG) {
                 uint4* const at = reinterpret_cast<uint4*>(recs + c * QS_LOW_CHUNK);
                 const uint4 x0 = at[0], x1 = at[1];
                 uint32_t v[8] = {x0.x, x0.y, x0.z, x0.w, x1.x, x1.y, x1.z, x1.w};
@@ -1453,7 +1473,7 @@ __device__ __forceinline__ void qs_body(const QSearchArgs& a, const GroupArgs& g
         __syncthreads();
         for (uint32_t k = 2u * QS_LOW_CHUNK; k <= P; k <<= 1) {
             for (uint32_t j = k >> 1; j >= QS_LOW_CHUNK; j >>= 1) {
-                for (uint32_t w = tid; w < P / 8u; w += QS_WG) {
+                for (uint32_t w = lt; w < P / 8u; w += QS_WG) {
                     const uint32_t t0 = 4u * w, i = ((t0 & ~(j - 1u)) << 1) | (t0 & (j - 1u));       // (four pairs side by side: j >= 8)
                     uint4* const pa = reinterpret_cast<uint4*>(recs + i);
                     uint4* const pb = reinterpret_cast<uint4*>(recs + i + j);
@@ -1470,7 +1490,7 @@ __device__ __forceinline__ void qs_body(const QSearchArgs& a, const GroupArgs& g
         // (3) runs.  A lane takes C consecutive places -- C odd: the lanes' places fall into different banks --; a run belongs to the
         // lane that holds its head, its length is one, or found by bisection (the array is sorted: a run ends where the doc does)
         const uint32_t C = ((nrec + QS_WG - 1u) / QS_WG) | 1u;
-        const uint32_t i0 = min(tid * C, nrec), i1 = min(i0 + C, nrec);
+        const uint32_t i0 = min(lt * C, nrec), i1 = min(i0 + C, nrec);
         auto run_len = [&](uint32_t i, uint32_t doc) -> uint32_t {
             if (i + 1u >= nrec || recs[i + 1u] != doc) return 1u;
             uint32_t lo = i + 2u, hi = nrec;
@@ -1492,7 +1512,7 @@ __device__ __forceinline__ void qs_body(const QSearchArgs& a, const GroupArgs& g
             const uint32_t incl = scan16(v);
             const uint32_t r0 = (uint32_t)__builtin_amdgcn_readlane((int)incl, 15), r1 = (uint32_t)__builtin_amdgcn_readlane((int)incl, 31),
                            r2 = (uint32_t)__builtin_amdgcn_readlane((int)incl, 47);
-            const uint32_t row = lane >> 4;
+            const uint32_t row = llane >> 4;
             return incl + (row >= 1u ? r0 : 0u) + (row >= 2u ? r1 : 0u) + (row >= 3u ? r2 : 0u);
         };
         {
@@ -1507,21 +1527,27 @@ __device__ __forceinline__ void qs_body(const QSearchArgs& a, const GroupArgs& g
         __syncthreads();
         // (4)
         const uint32_t best_q = lsc[4];
-        const uint32_t cut = max(floor_q, rel_floor(best_q, pct));
+        // ((COOP) rel_floor's 64-bit comparison is made on the VALU against a constant in two vector registers, which the compiler set up
+        // at the kernel's start and kept -- the MEM instantiations at 16 columns spilled them: 12 bytes of scratch.  In 32 bits here:
+        // best_q <= QS_REC_CAP = 2^13 and the percentage is cut at 2^19 - 1, where the relative floor is above 5242 x best_q already --
+        // beyond any score, as with the uncut percentage: best_q < cut either way, and nothing else looks at cut then)
+        static_assert(!COOP || QS_REC_CAP <= (1u << 13), "the relative floor in 32 bits");
+        const uint32_t rel = COOP ? best_q * min(pct, (1u << 19) - 1u) / 100u : rel_floor(best_q, pct);
+        const uint32_t cut = max(floor_q, rel);
         if (best_q >= cut) {                                 // (uniform)
             // (5) lane t: S(t) = docs at or above the cut whose slot is >= t.  T is the slot where S reaches K; slot 255 holds every
             // score from 255 up, so there nothing is cut (a superset: at most 8192 / 255 docs).  With K or fewer docs nobody writes: T = 0
             const uint32_t cb = min(cut, 255u);
-            const uint32_t hm = tid >= cb ? lhist[tid] : 0u;
+            const uint32_t hm = lt >= cb ? lhist[lt] : 0u;
             const uint32_t wi = wave_incl(hm);
-            if (lane == 63u) lsc[tid >> 6] = wi;
+            if (llane == 63u) lsc[lt >> 6] = wi;
             __syncthreads();
-            const uint32_t t0 = lsc[0], t1 = lsc[1], t2 = lsc[2], t3 = lsc[3], wv = tid >> 6;
+            const uint32_t t0 = lsc[0], t1 = lsc[1], t2 = lsc[2], t3 = lsc[3], wv = lt >> 6;
             const uint32_t incl = wi + (wv >= 1u ? t0 : 0u) + (wv >= 2u ? t1 : 0u) + (wv >= 3u ? t2 : 0u);
             const uint32_t above = t0 + t1 + t2 + t3 - incl;                       // S(t + 1)
             if (above + hm >= kmax && above < kmax) {
-                lsc[5] = tid == 255u ? 254u : tid;
-                lsc[6] = tid == 255u ? 0u : kmax - above;
+                lsc[5] = lt == 255u ? 254u : lt;
+                lsc[6] = lt == 255u ? 0u : kmax - above;
             }
             __syncthreads();
             const uint32_t tcut = lsc[5], quota = lsc[6];
@@ -1530,7 +1556,7 @@ __device__ __forceinline__ void qs_body(const QSearchArgs& a, const GroupArgs& g
                 uint32_t mine = 0u;
                 for_runs([&](uint32_t, uint32_t len) { mine += len == tcut ? 1u : 0u; });
                 const uint32_t mi = wave_incl(mine);
-                if (lane == 63u) lsc[tid >> 6] = mi;         // (the totals above were read before the last barrier)
+                if (llane == 63u) lsc[lt >> 6] = mi;         // (the totals above were read before the last barrier)
                 __syncthreads();
                 rank = mi - mine + (wv >= 1u ? lsc[0] : 0u) + (wv >= 2u ? lsc[1] : 0u) + (wv >= 3u ? lsc[2] : 0u);
             }
@@ -1766,7 +1792,7 @@ __device__ __forceinline__ void qs_body(const QSearchArgs& a, const GroupArgs& g
   }
 }
 
-// The nine kernels (the head comment's table): a wrapper names what is on.
+// The ten kernels (the head comment's table): a wrapper names what is on.
 template <int NS, bool QS, bool MEM, bool FILT>
 __global__ __launch_bounds__(QS_WG) FPX_QS_OCC void k_search_query(QSearchArgs a, GroupArgs ga)
 {
@@ -1791,6 +1817,11 @@ template <int NS, bool QS, bool MEM>
 __global__ __launch_bounds__(QS_WG) FPX_QS_OCC void k_search_filt(QSearchArgs a, GroupArgs ga)
 {
     qs_body<qs_variant<NS, QS, MEM, true, QS_F_COOP>>(a, ga);
+}
+template <int NS, bool QS, bool MEM>
+__global__ __launch_bounds__(QS_WG) FPX_QS_OCC void k_search_low_coop(QSearchArgs a, GroupArgs ga)
+{
+    qs_body<qs_variant<NS, QS, MEM, true, QS_F_LOW | QS_F_COOP>>(a, ga);
 }
 template <int NS, bool QS, bool FILT>
 __global__ __launch_bounds__(QS_WG) FPX_QS_OCC void k_search_next(QSearchArgs a, GroupArgs ga)

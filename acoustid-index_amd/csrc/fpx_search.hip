@@ -13,7 +13,7 @@
 //      (run_query_wg; run_side_wg for the file segments next to the group; run_words_wg -- option words_wg, k_search_words in
 //      fpx_qwords.hpp -- for a snapshot that is one group in directory + words form).  A batch with queries whose floor is 1 or 2 is B's,
 //      or -- option low_wg: 1 an unfiltered packed group, 2 a filtered one too -- run_query_wg's with k_search_low (k_search_low_filt) in
-//      k_search_query's place.  A snapshot of SEVERAL packed groups is B's, or -- option groups_wg = 1 -- run_query_wg's: the groups walked
+//      k_search_query's place (3: as 2, with k_search_low_coop where filt_coop = 1 would run k_search_filt).  A snapshot of SEVERAL packed groups is B's, or -- option groups_wg = 1 -- run_query_wg's: the groups walked
 //      one after the other, k_search_query over the first, k_search_next over the others, one k_finish.  Both together -- several groups
 //      and a low floor in the batch -- are B's, or, option groups_wg = 2 with low_wg, run_query_wg's: k_search_low (k_search_low_filt)
 //      over the first group, k_search_low_next over the others.
@@ -717,11 +717,12 @@ static bool group_filtered(const GroupDesc& gd) { return gd.any_dead != 0u || gd
 // docs -- the resident index between merges --, the queries short enough for their hash set and their floor above the legacy protocol's.
 // Option query_wg 2: a group with superseded docs or columns outside the snapshot too, by the kernel's filtered instantiation (*filt).
 // Option low_wg 1: queries with a floor of 1 or 2 too, where the group is NOT filtered (*low: the batch has such a query -- k_search_low);
-// 2: where it is filtered too (k_search_low_filt; a filtered group is only ever here under query_wg 2).
+// 2: where it is filtered too (k_search_low_filt; a filtered group is only ever here under query_wg 2); 3: as 2 -- which kernel a filtered
+// group's batch then gets is run_query_wg's business (k_search_low_coop where k_search_filt would be taken, else k_search_low_filt).
 static bool low_floors_ok(const Ctx* ctx, bool filtered)
 {
     const int64_t low_wg = ctx_opt(ctx, OPT_LOW_WG);
-    return low_wg == 2 || (low_wg == 1 && !filtered);
+    return low_wg == 2 || low_wg == 3 || (low_wg == 1 && !filtered);
 }
 // Option groups_wg 1: a snapshot of 2 .. QS_MAX_GROUPS packed groups too -- every one whole-hash-space, nothing else next to them --, walked
 // one after the other (run_query_wg: k_search_next).  *filt: ANY of them is filtered (under query_wg 2 only, as for one); no query with a
@@ -856,8 +857,8 @@ static int redo_hot_queries(Batch& b, QSearchArgs qa, const GroupArgs& gargs, bo
 
 // Dedup, probe, count and floor happen in ONE kernel, no keys are made or ordered, no record reaches HBM.  A batch that kernel hands back
 // (hot hashes: a query's records outgrow its LDS array) returns FPX_REDO_QS: run_with_redos gives it to the pipeline.
-// low: the batch has queries with a floor of 1 or 2 (option low_wg let it in; with filt under low_wg 2 only) -- k_search_low, or
-// k_search_low_filt on a filtered group; neither has a redo list.
+// low: the batch has queries with a floor of 1 or 2 (option low_wg let it in; with filt under low_wg 2 or 3 only) -- k_search_low, or
+// k_search_low_filt on a filtered group (low_wg 3: k_search_low_coop where `coop` holds); none of them has a redo list.
 // Every other batch is k_search_query's exactly as before, whatever that option says.
 // SEVERAL GROUPS (option groups_wg = 1; takes_query_wg): per upload piece the groups are walked one after the other on the batch's stream --
 // k_search_query over group 0 (with the memory segments' table), k_search_next over groups 1.., which chain their candidates behind the
@@ -899,7 +900,9 @@ static int run_query_wg(Batch& b, bool filt, bool low)
     // (option filt_coop = 1: ONE filtered packed group, no low floor in the batch, by k_search_filt -- where the snapshot holds the group's
     // union dead-set bitmap (made under filt_coop = 1, the id range narrow enough) or no column has a dead set.  The bitmap shares the
     // redo list's storage, which the filtered form never reads: fpx_qsearch.hpp, QSearchArgs)
-    const bool coop = filt && !low && ngroups == 1u && ctx_opt(snap->ctx, OPT_FILT_COOP) == 1 &&
+    // (option low_wg = 3: a batch WITH a low floor too, by k_search_low_coop -- the same rounds and tasks with k_search_low's sorted tail;
+    // under low_wg = 2 such a batch stays k_search_low_filt's, whatever filt_coop says)
+    const bool coop = filt && (!low || ctx_opt(snap->ctx, OPT_LOW_WG) == 3) && ngroups == 1u && ctx_opt(snap->ctx, OPT_FILT_COOP) == 1 &&
                       (snap->h_group[0].any_dead == 0u || (snap->dead_union && snap->dead_union->d_bits != nullptr));
     if (coop && snap->h_group[0].any_dead != 0u) {
         qa.dead_union = snap->dead_union->d_bits; qa.dead_union_last = (uint32_t)(snap->dead_union->words - 1u);
@@ -920,7 +923,8 @@ static int run_query_wg(Batch& b, bool filt, bool low)
         if (up_chunks) FPX_HIP(hipStreamWaitEvent(st, ws->ev_chunk[c], 0));           // (the piece's hashes have arrived; the next piece is on its way)
         const dim3 grid(std::min<uint32_t>(qa.q_end - qa.q_begin, (uint32_t)cus * QS_WGS_PER_CU));
         // (the piece's queries over group 0 -- filtered or not as that group is: with one group, takes_query_wg's `filt` --, with the memory table)
-        if (low && filt0) FPX_LAUNCH_QS(k_search_low_filt, grid, st, qa, gargs, ns8, b.want_q, mem);
+        if (low && coop) FPX_LAUNCH_QS(k_search_low_coop, grid, st, qa, gargs, ns8, b.want_q, mem);
+        else if (low && filt0) FPX_LAUNCH_QS(k_search_low_filt, grid, st, qa, gargs, ns8, b.want_q, mem);
         else if (low) FPX_LAUNCH_QS(k_search_low, grid, st, qa, gargs, ns8, b.want_q, mem);
         else if (coop) FPX_LAUNCH_QS(k_search_filt, grid, st, qa, gargs, ns8, b.want_q, mem);
         else FPX_LAUNCH_QS(k_search_query, grid, st, qa, gargs, ns8, b.want_q, mem, filt0);

@@ -61,11 +61,13 @@ class Context:
         that path (Stats.path_flags bit 10).  'words_wg': 0 | 1 | 2 -- a snapshot that is one group in directory + words form (every group
         that is not packed) searched by the pipeline | a query per workgroup (Stats.path_flags bit 11) | as 1, a group with superseded
         docs or masked columns too (bits 11 and 8); read when a snapshot is made as well: part 0 of a snapshot in two parts may then be
-        such a group.  'low_wg': 0 | 1 | 2 -- a batch with queries whose score floor is 1 or 2 (the legacy protocol's min_score 1, default
+        such a group.  'low_wg': 0 | 1 | 2 | 3 -- a batch with queries whose score floor is 1 or 2 (the legacy protocol's min_score 1, default
         floors of queries of 40 hashes or fewer) is the pipeline's | stays on the query-per-workgroup path of a packed, unfiltered group:
         such queries' records are sorted in LDS and only what finish can return is handed over (Stats.path_flags bit 12, with bits 6
         and 2; 'hot_wg' is ignored for such a batch) | as 1, and on a group with superseded docs or masked columns too, which only
-        'query_wg' 2 puts on that path (bits 12 and 8).  'groups_wg': 0 | 1 | 2 -- a snapshot of several packed groups keeps the largest for
+        'query_wg' 2 puts on that path (bits 12 and 8) | as 2, and where 'filt_coop' 1 would walk ONE such group eight lanes to a line --
+        its snapshot holds the union bitmap, or it has no dead set -- a batch with such floors is walked that way too, with the same
+        sorted tail (bits 12, 16 and 8); everything else as under 2.  'groups_wg': 0 | 1 | 2 -- a snapshot of several packed groups keeps the largest for
         the query-per-workgroup path and sends the others through the pipeline | walks up to 8 of them one after the other a query per
         workgroup, one finish (Stats.path_flags bit 13, with bits 6 and 2; read when a snapshot is made as well: part 0 of a snapshot in
         two parts then holds all such groups) | as 1, and a batch with queries whose score floor is 1 or 2 is walked that way too where

@@ -94,8 +94,9 @@ typedef struct {
                                    query per workgroup ("words_wg" 1 | 2; bit 2 is set with it, bit 8 when its filtered form ran, bit 6
                                    -- k_search_query's -- is not),
                                    bit 12: the batch (or its part 0) ran k_search_low: it has queries with a score floor of 1 or 2 and
-                                   stayed a query per workgroup ("low_wg" 1 | 2; bits 6 and 2 are set with it, and bit 8 when the group is
-                                   filtered -- k_search_low_filt, "low_wg" 2 under "query_wg" 2),
+                                   stayed a query per workgroup ("low_wg" 1 | 2 | 3; bits 6 and 2 are set with it, and bit 8 when the group
+                                   is filtered -- k_search_low_filt, "low_wg" 2 under "query_wg" 2; with bit 16 too k_search_low_coop,
+                                   "low_wg" 3),
                                    bit 13: the batch (or its part 0) walked SEVERAL packed groups a query per workgroup, one after the
                                    other -- k_search_query over the first, k_search_next over the others, one k_finish ("groups_wg" 1;
                                    bits 6 and 2 are set with it, and bit 8 when any of the groups is filtered).  Bits 13 and 12
@@ -107,7 +108,8 @@ typedef struct {
                                    under "shard_wg"; bits 14, 6 and 4 are set with it).  fpx_sharded_search_batch: when every device's was,
                                    bit 16: the batch (or its part 0) ran k_search_filt -- the filtered form eight lanes to a line, behind
                                    the group's union dead-set bitmap ("filt_coop" 1 under "query_wg" 2; bits 8 and 6 are set with it, and
-                                   bit 7 where it was part 0 of a snapshot in two parts) */
+                                   bit 7 where it was part 0 of a snapshot in two parts) -- or, with bit 12, k_search_low_coop: the same
+                                   walk with k_search_low's sorted tail, for a batch with a score floor of 1 or 2 ("low_wg" 3) */
     uint64_t probe_kernel_fetched_bytes; /* block bytes the main probe kernel really fetched, in 128-byte lines: a probe
                                    whose hash the segment's presence bits know to be absent counts as a visited block (as in
                                    the reference) without the block being read, and a block that is read costs two lines up
@@ -161,7 +163,7 @@ int  fpx_ctx_device(const fpx_ctx *ctx);     /* the HIP ordinal the context live
  *                        the snapshot's next 32 batches stay there.  Read when a snapshot is made too: with no packed group to be
  *                        part 0 of a snapshot in two parts (bit 7), the largest group in this form may be -- whole, and unfiltered
  *                        unless the value is 2; a snapshot made under 0 is searched as before whatever the option says later
- *   "low_wg"             0 | 1 | 2   a batch with queries whose score floor is 1 or 2 -- the legacy protocol's min_score 1, the default
+ *   "low_wg"             0 | 1 | 2 | 3   a batch with queries whose score floor is 1 or 2 -- the legacy protocol's min_score 1, the default
  *                        floor of a query of 40 hashes or fewer -- is the pipeline's, whatever the snapshot (default 0) | stays a QUERY
  *                        PER WORKGROUP where "query_wg" would have taken it but for those floors: ONE packed group, unfiltered (a
  *                        filtered group under "query_wg" 2 keeps the pipeline for such a batch), or such a part 0 of a snapshot in
@@ -173,6 +175,12 @@ int  fpx_ctx_device(const fpx_ctx *ctx);     /* the HIP ordinal the context live
  *                        so does such a batch on a FILTERED group -- superseded docs and/or columns outside the snapshot, which
  *                        "query_wg" 2 alone puts on this path; with "query_wg" 1 the value 2 is 1 --, by k_search_low_filt (bits 12
  *                        and 8): the filtered walk leaves live docs only for the same sorted tail.  On an unfiltered group 2 is 1
+ *                        | as 2, and where "filt_coop" 1 would give the group to k_search_filt -- ONE filtered packed group (or
+ *                        such a part 0) whose snapshot, made under "filt_coop" 1, holds the union dead-set bitmap, or which has no
+ *                        dead set; "query_wg" 2 and "filt_coop" 1 in force -- such a batch runs k_search_low_coop (bits 12, 16 and
+ *                        8): k_search_filt's rounds, eight lanes to a line behind the bitmap, and the same sorted tail.  A
+ *                        snapshot made under "filt_coop" 0, an id range beyond 2^29, several groups ("groups_wg" 2) and an
+ *                        unfiltered group behave under 3 exactly as under 2.  Results and statistics are the same under 2 and 3
  *   "groups_wg"          0 | 1 | 2   a snapshot of SEVERAL packed groups -- an index with more dense segments than one group's 16 columns,
  *                        merge results that met and formed a group of their own -- keeps its largest group for k_search_query (part 0
  *                        of two parts) and sends the others through the pipeline; a snapshot that is nothing but such groups is the
@@ -229,7 +237,7 @@ int  fpx_ctx_device(const fpx_ctx *ctx);     /* the HIP ordinal the context live
  *                        (the kernel: k_search_filt where the snapshot holds the bitmap or the group has no dead set).  A snapshot
  *                        made under 0, or one whose id range was too wide, keeps the filtered k_search_query under 1.  Results and
  *                        statistics are the same.  Values above 1 are refused.  The other filtered walks stay as they are under
- *                        either value: k_search_low_filt ("low_wg" 2), k_search_next / k_search_low_next on filtered groups
+ *                        either value: k_search_low_filt ("low_wg" 2; "low_wg" 3 is its eight-lanes form), k_search_next / k_search_low_next on filtered groups
  *                        ("groups_wg"), k_search_window / k_search_packed ("shard_wg" 2), k_search_words ("words_wg" 2) and the
  *                        pipeline's k_probe_pgroup.  Without "query_wg" 2 the option does nothing
  *   "fast"              1 | 0   the device-sized path (one host round trip per batch; default 1)
